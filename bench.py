@@ -8,6 +8,17 @@ FRAMES_PER_STEP frames over the whole image (inputs resident in HBM), ending
 with the tile gather to rank 0 when N > 1.
 
   python bench.py [--gpus N] [--steps K] [--warmup W] [--frames-per-step F] [--config C1..C5]
+                  [--full] [--dump-outputs DIR]
+
+A plain run sets up, warms up, times the K steps and prints the line with the
+headline figure (metric, value, unit, ms_per_step, config, build).  --full
+adds everything else described below to the same line: ray rates, the strong /
+samples-weak views, the interactive cadence, the roofline, the self-check
+(verified) and the CPU baseline, each with runs of its own outside the timed
+steps.  --dump-outputs DIR writes what the last timed step left on rank 0
+(accumulation, RGBA8 and depth images) as DIR/<name>.npy, float32, read
+before anything else renders; scene, camera and per-frame times depend only
+on the arguments, so two builds can be compared array for array.
 
 --config runs the same measurement on another BASELINE.json configuration
 (C1 Cornell + example sphere 512x512, C3 HDRI + textured knot 1280x720, C4
@@ -252,6 +263,39 @@ def self_check(r, scene: dict, F: int, svc_mode: int, world: int, red_dev) -> di
                     "agree when verified)"}
 
 
+# ---- outputs of the timed path ---------------------------------------------------
+DUMP_BUDGET_BYTES = 60_000_000
+DUMP_SAMPLE_SEED = 20240607
+
+
+def dump_outputs(r, out_dir: str) -> dict:
+    """Write what a caller of the timed path reads back after its last step:
+    the float4 accumulation (accum), the tonemapped RGBA8 image (rgba8) and
+    the depth image (depth8), each as <out_dir>/<name>.npy in float32 with
+    shape (pixels, 4).  Every pixel in row-major order while the three arrays
+    fit DUMP_BUDGET_BYTES together; else the same fixed, seeded sample of
+    pixels (sorted row-major indices) of each."""
+    import numpy as np
+    arrays = {"accum": r.read_accum(), "rgba8": r.read_rgba8(), "depth8": r.read_depth8()}
+    n_pix = r.width * r.height
+    keep = DUMP_BUDGET_BYTES // (16 * len(arrays))
+    index = None
+    if n_pix > keep:
+        index = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(n_pix, size=keep, replace=False))
+    os.makedirs(out_dir, exist_ok=True)
+    total = 0
+    for name, a in arrays.items():
+        a = a.reshape(n_pix, 4)
+        if index is not None:
+            a = a[index]
+        a = np.ascontiguousarray(a, dtype=np.float32)
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+        total += a.nbytes
+    return {"dir": out_dir, "arrays": sorted(arrays), "dtype": "float32", "pixels": int(min(n_pix, keep)),
+            "of_pixels": int(n_pix), "bytes": int(total),
+            "sample": None if index is None else f"numpy default_rng({DUMP_SAMPLE_SEED}).choice, sorted"}
+
+
 # ---- main ---------------------------------------------------------------------
 def main():
     ap = argparse.ArgumentParser()
@@ -279,6 +323,13 @@ def main():
     ap.add_argument("--no-verify", action="store_true",
                     help="skip the self-check after the timed loop (profiling runs: the timed dispatches are then "
                          "the run's last ones, as scripts/summarize_round.py assumes)")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the timed steps: the counting and instrumented steps, the vector-memory roof, the "
+                         "self-check, the strong / samples-weak and interactive measurements, the roofline and the "
+                         "CPU baseline (the options above that trim them apply only here)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last one left (accumulation, RGBA8 and depth images "
+                         "of rank 0) as DIR/<name>.npy in float32")
     ap.add_argument("--check-launch", action="store_true",
                     help="form the process group over gloo, count the ranks and exit (no GPU; tests the launcher)")
     args = ap.parse_args()
@@ -351,17 +402,17 @@ def main():
     # algorithm's events (strict traversal, no primary-hit reuse, no last-
     # bounce shortcut) for the survey's byte pricing and Mrays/s; (2) the
     # memory operations the production kernels execute, for the roofline
-    r.set_strict_traversal(True)
-    ref_counts = r.render_counted(frames=F, time_seed=scene["time"])
-    r.set_strict_traversal(False)
-    r.clearBuffer()
-    exec_counts = r.render_profiled(frames=F, time_seed=scene["time"])
-    r.clearBuffer()
-    r.sync()
-
-    roof = None
-    if rank == 0 and not args.no_roof:
-        roof = vmem_roof(gpu)
+    ref_counts = exec_counts = roof = None
+    if args.full:
+        r.set_strict_traversal(True)
+        ref_counts = r.render_counted(frames=F, time_seed=scene["time"])
+        r.set_strict_traversal(False)
+        r.clearBuffer()
+        exec_counts = r.render_profiled(frames=F, time_seed=scene["time"])
+        r.clearBuffer()
+        r.sync()
+        if rank == 0 and not args.no_roof:
+            roof = vmem_roof(gpu)
 
     def step(i):
         times = [scene["time"] + i * F + k for k in range(F)]
@@ -393,6 +444,44 @@ def main():
 
     wr = (W // 16) * 16
     hr = (H // 16) * 16
+    paths_per_step = wr * hr * 2 * F
+    total_paths = paths_per_step * args.steps
+    value = total_paths / elapsed / 1e6
+
+    # what the last timed step left, read before anything renders again
+    dumped = dump_outputs(r, args.dump_outputs) if (args.dump_outputs and rank == 0) else None
+
+    head = {
+        "metric": METRIC,
+        "value": round(value, 3),
+        "unit": "Mpaths/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": round(elapsed / args.steps * 1e3, 4),
+        "higher_is_better": True,
+        "scaling": scaling,
+        "vs_baseline": None,
+        "dtype": "f32",
+        "data": WORKLOADS[CFG][1],
+        "config": {"workload": WORKLOADS[CFG][0], "width": W, "height": H, "frames_per_step": F,
+                   "paths_per_step": paths_per_step, "parallelism": f"tile{world}",
+                   "gather": (("RCCL ncclGather (C ABI vrhip_comm_gather)" if backend == "nccl" else
+                               backend + " gather (host-staged rehearsal)")
+                              + " of RGBA8 tiles to rank 0 per step") if world > 1 else "none"},
+        "full": bool(args.full),
+        "outputs": dumped,
+    }
+    if not args.full:
+        # a plain run: the timed steps and their line, nothing else
+        if rank == 0:
+            head["build"] = build_id()
+            print(json.dumps(head), flush=True)
+        gather.close()
+        r.cleanUp()
+        if world > 1:
+            dist.destroy_process_group()
+        return
 
     # self-check of the timed path: the first VERIFY_STEPS steps of the timed
     # loop rendered again from a cleared accumulation, once on the render
@@ -523,9 +612,6 @@ def main():
         dist.all_reduce(cvec)
     tot = {k: float(v) for k, v in zip(keys + ["owned_pixels"], cvec.tolist())}
 
-    paths_per_step = wr * hr * 2 * F
-    total_paths = paths_per_step * args.steps
-    value = total_paths / elapsed / 1e6
     rays_per_path = tot["rays"] / paths_per_step
     mrays = value * rays_per_path
     # rays the production kernels trace (the instrumented copy's own count:
@@ -624,24 +710,8 @@ def main():
                             "live-measured gather roof (vrhip_microbench_vmem, best of 1..64 addresses per "
                             "wave-instruction); bound = the roof with the largest fraction; traffic = physical "
                             "HBM bytes per launch (rocprofv3 PMC, traffic_source)"}
-        out = {
-            "metric": METRIC,
-            "value": round(value, 3),
-            "unit": "Mpaths/s",
-            "n_gpus": world,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": round(elapsed / args.steps * 1e3, 4),
-            "higher_is_better": True,
-            "scaling": scaling,
-            "vs_baseline": None,
-            "dtype": "f32",
-            "data": WORKLOADS[CFG][1],
-            "config": {"workload": WORKLOADS[CFG][0], "width": W, "height": H, "frames_per_step": F,
-                       "paths_per_step": paths_per_step, "parallelism": f"tile{world}",
-                       "gather": (("RCCL ncclGather (C ABI vrhip_comm_gather)" if backend == "nccl" else
-                                   backend + " gather (host-staged rehearsal)")
-                                  + " of RGBA8 tiles to rank 0 per step") if world > 1 else "none"},
+        out = dict(head)
+        out.update({
             "mrays_per_s": round(mrays, 3),
             "rays_per_path": round(rays_per_path, 4),
             "mrays_per_s_traced": round(value * rays_per_path_traced, 3),
@@ -661,7 +731,7 @@ def main():
             "verified": verify["verified"],
             "verify": verify,
             "build": build_id(),
-        }
+        })
         if not args.no_cpu and world == 1:
             out["cpu_baseline"] = cpu_baseline(scene, args.cpu_budget)
         else:

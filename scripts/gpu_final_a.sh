@@ -11,8 +11,8 @@ step() {
 }
 step pytest 480 python3 -u -m pytest tests -m gpu -rA -v --timeout 300 --timeout-method thread
 step smoke 120 python3 -c "import __graft_entry__ as g; g.smoke()"
-step bench_C2 300 python3 bench.py
+step bench_C2 300 python3 bench.py --full
 for cfg in C1 C3 C4 C5 C2D C3D; do
-  step bench_$cfg 300 python3 bench.py --config $cfg --no-cpu
+  step bench_$cfg 300 python3 bench.py --full --config $cfg --no-cpu
 done
 exit 0

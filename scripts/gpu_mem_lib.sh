@@ -5,7 +5,7 @@
 set -o pipefail
 cd "$GRAFT_REPO_ROOT"
 TAG=$1; CFG=$2; export VRHIP_LIB=$(readlink -f $3); OUT=gpurun_out/$TAG; mkdir -p $OUT; export TMPDIR=/tmp
-BENCH="bench.py --steps 3 --warmup 1 --no-cpu --no-roof --interactive-frames 0 --strong-steps 0 --config $CFG"
+BENCH="bench.py --full --steps 3 --warmup 1 --no-cpu --no-roof --interactive-frames 0 --strong-steps 0 --config $CFG"
 i=0
 for PMC in "GRBM_GUI_ACTIVE TA_TA_BUSY_sum" "TD_TD_BUSY_sum TA_ADDR_STALLED_BY_TC_CYCLES_sum" \
            "SQ_WAVES SQ_INSTS_VALU SQ_INSTS_VMEM_RD SQ_INSTS_LDS SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_ACTIVE_INST_VALU SQ_THREAD_CYCLES_VALU"; do

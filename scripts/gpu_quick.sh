@@ -20,6 +20,6 @@ if [ -z "$NO_TESTS" ]; then
   step smoke 120 python3 -c "import __graft_entry__ as g; g.smoke()"
 fi
 for cfg in $CFGS; do
-  step bench_$cfg 300 python3 bench.py --config $cfg --no-cpu
+  step bench_$cfg 300 python3 bench.py --full --config $cfg --no-cpu
 done
 exit 0

@@ -24,11 +24,11 @@ if [ "$2" != "--no-tests" ]; then
   step pytest 480 python3 -u -m pytest tests -m gpu -rA -v --timeout 300 --timeout-method thread
   step smoke 120 python3 -c "import __graft_entry__ as g; g.smoke()"
 fi
-step bench_C2 300 python3 bench.py
+step bench_C2 300 python3 bench.py --full
 for cfg in C1 C3 C4 C5 C2D C3D; do
-  step bench_$cfg 300 python3 bench.py --config $cfg --no-cpu
+  step bench_$cfg 300 python3 bench.py --full --config $cfg --no-cpu
 done
-PB="bench.py --steps 5 --warmup 1 --no-cpu --no-roof --interactive-frames 0 --strong-steps 0"
+PB="bench.py --full --steps 5 --warmup 1 --no-cpu --no-roof --interactive-frames 0 --strong-steps 0"
 for cfg in C1 C2 C3 C4 C5; do
   step trace_$cfg 200 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace_$cfg -o run -- python3 $PB --config $cfg
   step fetch_$cfg 200 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $OUT/fetch_$cfg -o run -- python3 $PB --config $cfg

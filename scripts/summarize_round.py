@@ -139,7 +139,7 @@ def main():
     prof = os.path.join(REPO, "profiles")
     md = [f"# Profile {name}\n",
           f"Source: `scripts/gpu_round.sh` on one MI355X (`{os.path.basename(src.rstrip('/'))}`); "
-          "rocprofv3 runs of `bench.py --steps 5 --warmup 1 --no-cpu --no-roof --interactive-frames 0 --config <C>`; "
+          "rocprofv3 runs of `bench.py --full --steps 5 --warmup 1 --no-cpu --no-roof --interactive-frames 0 --config <C>`; "
           f"durations and counters averaged over the {STEPS} timed dispatches of each production kernel "
           "(warmup and the untimed counting kernels excluded).\n"]
     for cfg in ("C1", "C2", "C3", "C4", "C5"):

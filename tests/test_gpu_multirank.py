@@ -108,7 +108,7 @@ def test_bench_two_ranks_gloo_rehearsal(native):
     the two ranks itself (they share cuda:0 over gloo here)."""
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     env.update(VRHIP_DIST_BACKEND="gloo", MASTER_ADDR="127.0.0.1")
-    cmd = [sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
+    cmd = [sys.executable, os.path.join(REPO, "bench.py"), "--full", "--gpus", "2", "--steps", "2", "--warmup", "1",
            "--frames-per-step", "2", "--no-cpu", "--no-roof", "--interactive-frames", "2", "--strong-steps", "2"]
     res = subprocess.run(cmd, cwd=REPO, env=env, capture_output=True, text=True, timeout=600)
     assert res.returncode == 0, res.stderr[-3000:]
