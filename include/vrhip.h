@@ -124,6 +124,34 @@ int vrhip_upload_mesh_flat(vrhip_ctx *ctx,
 int vrhip_upload_mesh_indexed(vrhip_ctx *ctx, const float *positions, const float *normals,
                               const float *tangents, const float *uvs, uint32_t n_verts,
                               const uint32_t *tris, uint32_t n_tris, uint32_t max_leaf_tris);
+/* The same mesh from arrays that already live on the context's device (no
+ * reference counterpart: the reference builds on the host, src/SBVH.cpp).
+ * Every pointer is a device pointer; d_normals, d_tangents and d_uvs may be
+ * NULL (zeros, as vrhip_build_flat); max_leaf_tris 0 means 2, at most 127.
+ * The tree is built on the device: triangles in Morton order of their box
+ * centres (ties by index), L = max(2, ceil(n_tris / max_leaf_tris)) leaves of
+ * equal size (+-1), inner nodes halving the leaf range, depth ceil(log2 L); a
+ * single triangle is stored twice under two leaves, as the host builder does.
+ * The caller's data must be complete before the call; the build runs on the
+ * context stream and the call returns when it has finished.  Transactional:
+ * on any error the resident mesh stays as it was.  VRHIP_ERR_INVALID for null
+ * or empty arrays, n_tris >= 2^24, max_leaf_tris > 127 (all before any device
+ * call), an index >= n_verts or a non-finite position of a referenced vertex
+ * (both found on the device), and on a vrhip_create_multi context (the
+ * pointers live on one device).  Added without an ABI version change: ABI 6
+ * gained this symbol, vrhip_export_mesh_flat and vrhip_selftest_half_box and
+ * changed no other. */
+int vrhip_upload_mesh_device(vrhip_ctx *ctx, const float *d_positions, const float *d_normals,
+                             const float *d_tangents, const float *d_uvs, uint32_t n_verts,
+                             const uint32_t *d_tris, uint32_t n_tris, uint32_t max_leaf_tris);
+/* The resident mesh, whichever upload call brought it, rewritten on the host
+ * in the reference layout vrhip_upload_mesh_flat takes (what the oracle, or a
+ * caller caching a tree, needs of a device-built tree).  Nodes are numbered
+ * by the LIFO flatten of vrhip_build_flat, so a tree that call made comes
+ * back byte for byte; vertex .w is 0.  Call with NULL arrays for the sizes.
+ * VRHIP_ERR_INVALID with no mesh loaded.  Synchronous. */
+int vrhip_export_mesh_flat(vrhip_ctx *ctx, float *bvh, size_t *n_bvh_f4, float *verts, float *normals,
+                           float *tangents, float *uvs, size_t *n_slots);
 /* replaces vRendererCuda::loadHDR (src/vRendererCuda.cpp:320-340) +
  * cu_setHDRDim: rgba float4[w*h] (or half4 with the _half variant, the
  * Imf::Rgba layout, converted on the device). */
@@ -286,7 +314,8 @@ int vrhip_set_overlap(vrhip_ctx *ctx, int mode);
  *   vrhip_sync, vrhip_read_accum/rgba8/depth8, vrhip_device_buffers,
  *   vrhip_gl_present, vrhip_pack_tiles/unpack_tiles, vrhip_last_kernel_ms,
  *   vrhip_kernel_stats, vrhip_debug_counters, vrhip_set_camera, vrhip_clear,
- *   every upload, vrhip_set_stream, vrhip_set_tiling, vrhip_set_service
+ *   every upload (vrhip_upload_mesh_device too), vrhip_export_mesh_flat,
+ *   vrhip_set_stream, vrhip_set_tiling, vrhip_set_service
  *   (and its timing / budget hooks), vrhip_comm_init/destroy, vrhip_destroy,
  *   the counting renders, and a vrhip_render that does not fit the session.
  *   Calls that do NOT close it: the flag setters (Cornell box, example sphere,
@@ -431,6 +460,10 @@ int vrhip_bvh_info(vrhip_ctx *ctx, uint32_t *depth, uint32_t *n_nodes, uint32_t 
 /* Evaluate the device libm on n inputs (test hook: 0 sin, 1 cos, 2 acos,
  * 3 atan2, 4 pow, 5 fmin, 6 fmax, 7 f2i); a,b,out host arrays of n floats. */
 int vrhip_selftest_math(int device, int fn, const float *a, const float *b, float *out, size_t n);
+/* The device BVH builder's outward fp32 -> fp16 box rounding on n host
+ * floats (test hook): down[i] rounded toward -inf, up[i] toward +inf, as
+ * binary16 bit patterns. */
+int vrhip_selftest_half_box(int device, const float *in, size_t n, uint16_t *down, uint16_t *up);
 /* Compare the kernels' reciprocal (rcp_rn: v_rcp_f32 + one Newton step, used
  * for 1/det in the triangle test) with IEEE 1/x for every float bit pattern in
  * [lo_bits, hi_bits) and its negation (test hook; hi_bits <= 2^31).

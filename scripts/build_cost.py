@@ -1,0 +1,123 @@
+#!/usr/bin/env python3
+"""Cost of getting a mesh into the renderer: the BVH built on the device from
+device-resident triangles (initMeshDevice) against the host path (build_flat,
+then initMesh), and what the device's simpler tree costs at render time.
+
+  python scripts/build_cost.py [--out build_cost.json] [--frames 16] [--steps 4]
+
+One JSON line per mesh (the 10k-triangle knot in scene C2, the 1M-triangle knot
+in scene C5):
+  device_build_ms   median of 5 builds into fresh contexts after one warm-up,
+                    wall clock around the synchronous call
+  host_build_flat_ms, host_init_mesh_ms   the host path in the same process
+  depth_device, depth_host                as vrhip_bvh_info reports them
+  mpaths_device_tree, mpaths_host_tree    frames-per-step render rate of the
+                    scene on each tree, measured as scripts/ab.py does (median
+                    of 3 batches of back-to-back steps)
+"""
+import argparse
+import json
+import os
+import sys
+import time
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, REPO)
+
+import numpy as np  # noqa: E402
+import torch  # noqa: E402
+
+from vrenderer_pathtracer_amd import VRendererHIP, build_flat, scenes  # noqa: E402
+
+
+def median(v):
+    v = sorted(v)
+    return v[len(v) // 2]
+
+
+def render_rate(r, sc, frames, steps):
+    r.render(frames=frames, time_seed=sc["time"])     # warm-up
+    r.clearBuffer()
+    ts = []
+    for b in range(3):
+        t0 = time.perf_counter()
+        for i in range(steps):
+            j = b * steps + i
+            r.render(frames=frames, times=[sc["time"] + j * frames + k for k in range(frames)], sync=False)
+        r.sync()
+        ts.append((time.perf_counter() - t0) / steps)
+    paths = (sc["width"] // 16) * 16 * (sc["height"] // 16) * 16 * 2 * frames
+    return paths / median(ts) / 1e6
+
+
+def measure(cfg, nu, nv, leaf, frames, steps):
+    mesh = scenes.torus_knot(nu, nv)
+    t0 = time.perf_counter()
+    flat = build_flat(mesh, max_leaf_tris=leaf)
+    host_build = time.perf_counter() - t0
+    scenes._MESH_CACHE[(nu, nv, leaf)] = flat          # the scene below takes this tree instead of building it again
+    sc = scenes.make_scene(cfg, knot=(nu, nv))
+    assert sc["mesh_flat"] is flat
+
+    r = VRendererHIP(0)
+    r.init(sc["width"], sc["height"])
+    t0 = time.perf_counter()
+    r.initMesh(flat)
+    host_init = time.perf_counter() - t0
+    depth_host = r.bvh_info()[0]
+    r.cleanUp()
+
+    dev = torch.device("cuda", 0)
+    d = {k: torch.from_numpy(np.ascontiguousarray(mesh[k])).to(dev) for k in ("positions", "normals", "tangents", "uvs")}
+    d["tris"] = torch.from_numpy(np.ascontiguousarray(mesh["tris"], np.int32)).to(dev)
+    torch.cuda.synchronize(dev)
+
+    def device_build(r):
+        r.initMeshDevice(d["positions"], d["tris"], d["normals"], d["tangents"], d["uvs"], max_leaf_tris=leaf)
+
+    builds = []
+    for i in range(6):                                 # the first is the warm-up
+        r = VRendererHIP(0)
+        r.init(sc["width"], sc["height"])
+        t0 = time.perf_counter()
+        device_build(r)
+        builds.append(time.perf_counter() - t0)
+        depth_dev = r.bvh_info()[0]
+        r.cleanUp()
+
+    r = VRendererHIP(0)
+    scenes.load_into(r, sc)
+    rate_host = render_rate(r, sc, frames, steps)
+    r.cleanUp()
+    r = VRendererHIP(0)
+    scenes.load_into(r, sc)
+    device_build(r)
+    rate_dev = render_rate(r, sc, frames, steps)
+    r.cleanUp()
+    return {"scene": cfg, "knot": [nu, nv], "n_tris": int(len(mesh["tris"])), "max_leaf_tris": leaf,
+            "device_build_ms": round(median(builds[1:]) * 1e3, 3),
+            "device_build_ms_all": [round(b * 1e3, 3) for b in builds[1:]],
+            "host_build_flat_ms": round(host_build * 1e3, 3), "host_init_mesh_ms": round(host_init * 1e3, 3),
+            "depth_device": depth_dev, "depth_host": depth_host, "frames_per_step": frames,
+            "mpaths_device_tree": round(rate_dev, 1), "mpaths_host_tree": round(rate_host, 1),
+            "render_rate_ratio": round(rate_dev / rate_host, 4)}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--out", default=None, help="also write the lines to this file")
+    ap.add_argument("--frames", type=int, default=16)
+    ap.add_argument("--steps", type=int, default=4)
+    a = ap.parse_args()
+    lines = []
+    for cfg, nu, nv, leaf in (("C2", 100, 50, 2), ("C5", 1000, 500, 4)):
+        lines.append(json.dumps(measure(cfg, nu, nv, leaf, a.frames, a.steps)))
+        print(lines[-1], flush=True)
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as f:
+            f.write("\n".join(lines) + "\n")
+
+
+if __name__ == "__main__":
+    main()

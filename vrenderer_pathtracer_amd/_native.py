@@ -54,6 +54,9 @@ _SIGNATURES = {
     "vrhip_upload_mesh_flat": (ctypes.c_int, [_ctx, _f, ctypes.c_size_t, _f, _f, _f, _f, ctypes.c_size_t]),
     "vrhip_upload_mesh_indexed": (ctypes.c_int, [_ctx, _f, _f, _f, _f, ctypes.c_uint32, _u32, ctypes.c_uint32,
                                                  ctypes.c_uint32]),
+    "vrhip_upload_mesh_device": (ctypes.c_int, [_ctx, _vp, _vp, _vp, _vp, ctypes.c_uint32, _vp, ctypes.c_uint32,
+                                                ctypes.c_uint32]),
+    "vrhip_export_mesh_flat": (ctypes.c_int, [_ctx, _f, _sz, _f, _f, _f, _f, _sz]),
     "vrhip_upload_hdr": (ctypes.c_int, [_ctx, _f, ctypes.c_uint32, ctypes.c_uint32]),
     "vrhip_upload_hdr_half": (ctypes.c_int, [_ctx, _u16, ctypes.c_uint32, ctypes.c_uint32]),
     "vrhip_upload_texture": (ctypes.c_int, [_ctx, ctypes.c_int, _f, ctypes.c_uint32, ctypes.c_uint32]),
@@ -101,6 +104,7 @@ _SIGNATURES = {
     "vrhip_set_service_budget": (ctypes.c_int, [_ctx, ctypes.c_size_t]),
     "vrhip_bvh_info": (ctypes.c_int, [_ctx, _u32, _u32, _u32]),
     "vrhip_selftest_math": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, _f, _f, _f, ctypes.c_size_t]),
+    "vrhip_selftest_half_box": (ctypes.c_int, [ctypes.c_int, _f, ctypes.c_size_t, _u16, _u16]),
     "vrhip_selftest_rcp": (ctypes.c_int, [ctypes.c_int, ctypes.c_uint32, ctypes.c_uint32,
                                           ctypes.POINTER(ctypes.c_uint64), _u32]),
     "vrhip_selftest_tonemap": (ctypes.c_int, [ctypes.c_int, ctypes.c_uint32, ctypes.c_uint32,

@@ -27,6 +27,7 @@
 
 #include "../../include/vrhip.h"
 #include "vr_bvh.hpp"
+#include "vr_devbvh.hpp"
 #include "vr_exr.hpp"
 #include "vr_merl.hpp"
 #include "vr_params.hpp"
@@ -268,6 +269,7 @@ constexpr size_t kSyncCtrBytes = (64u * vr::kSyncGroups + 64u) * sizeof(uint32_t
 #endif
 static void svc_free(vrhip_ctx* c);
 static int svc_close(vrhip_ctx* c);
+static int svc_verify(vrhip_ctx* c);
 static int refuse_multi(vrhip_ctx* c, const char* what);
 static int multi_gather(vrhip_ctx* c, int what);
 static int multi_images(vrhip_ctx* c);
@@ -816,6 +818,153 @@ int vrhip_upload_mesh_indexed(vrhip_ctx* c, const float* positions, const float*
     return vrhip_upload_mesh_flat(c, (const float*)m.bvh.data(), m.bvh.size(), (const float*)m.verts.data(),
                                   (const float*)m.normals.data(), (const float*)m.tangents.data(),
                                   (const float*)m.uvs.data(), m.verts.size());
+}
+
+// The device builder's entry point (vr_devbvh.hip): the eight arrays of the
+// device layout are built from device-resident triangles into fresh buffers and
+// swapped into the context only when the build succeeded, so a refused mesh
+// leaves the resident one as it was.
+namespace {
+struct DeviceBuild {
+    vr::DevBuildOut o{};
+    vr::DevBuildStatus* status = nullptr;
+    void* scratch = nullptr;
+    ~DeviceBuild()
+    {
+        dfree(o.bvh); dfree(o.bvh16); dfree(o.verts); dfree(o.tri_e); dfree(o.tpath);
+        dfree(o.normals); dfree(o.tangents); dfree(o.uvs); dfree(status);
+        if (scratch) (void)hipFree(scratch);
+    }
+};
+} // namespace
+
+int vrhip_upload_mesh_device(vrhip_ctx* c, const float* d_positions, const float* d_normals, const float* d_tangents,
+                             const float* d_uvs, uint32_t n_verts, const uint32_t* d_tris, uint32_t n_tris,
+                             uint32_t max_leaf_tris)
+{
+    if (!c) return fail(VRHIP_ERR_INVALID, "null ctx");
+    if (!d_positions || !d_tris || n_tris == 0 || n_verts == 0) return fail(VRHIP_ERR_INVALID, "null or empty mesh arrays");
+    if (n_tris >= (1u << (31 - kLeafCountBits))) return fail(VRHIP_ERR_INVALID, "more than 16M triangles");
+    if (max_leaf_tris >= (1u << kLeafCountBits)) return fail(VRHIP_ERR_INVALID, "max_leaf_tris above 127");
+    if (!c->group.empty()) return refuse_multi(c, "vrhip_upload_mesh_device");
+    const vr::DevBuildShape sh = vr::devbvh_shape(n_tris, max_leaf_tris ? max_leaf_tris : 2u);
+    int rc = set_device(c); if (rc) return rc;
+    quiesce(c);
+    DeviceBuild b;
+    const size_t nv = 3 * (size_t)sh.n_refs;
+    HIP_TRY(hipMalloc((void**)&b.o.bvh, 4 * (size_t)sh.nodes * 16));
+    HIP_TRY(hipMalloc((void**)&b.o.bvh16, 2 * (size_t)sh.nodes * 16));
+    HIP_TRY(hipMalloc((void**)&b.o.verts, nv * sizeof(vr3)));
+    HIP_TRY(hipMalloc((void**)&b.o.tri_e, nv * sizeof(vr3)));
+    HIP_TRY(hipMalloc((void**)&b.o.tpath, (size_t)sh.n_refs * sizeof(unsigned long long)));
+    HIP_TRY(hipMalloc((void**)&b.o.normals, nv * 16));
+    HIP_TRY(hipMalloc((void**)&b.o.tangents, nv * 16));
+    HIP_TRY(hipMalloc((void**)&b.o.uvs, nv * 8));
+    HIP_TRY(hipMalloc((void**)&b.status, sizeof(vr::DevBuildStatus)));
+    HIP_TRY(hipMemsetAsync(b.status, 0, sizeof(vr::DevBuildStatus), c->stream));
+    const int e = vr::devbvh_build(d_positions, d_normals, d_tangents, d_uvs, n_verts, d_tris, n_tris,
+                                   max_leaf_tris ? max_leaf_tris : 2u, b.o, b.status, &b.scratch, c->stream);
+    if (e) return fail(VRHIP_ERR_HIP, std::string("device BVH build: ") + hipGetErrorString((hipError_t)e));
+    vr::DevBuildStatus st{};
+    HIP_TRY(hipMemcpyAsync(&st, b.status, sizeof(st), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    if (st.flags & vr::DEVBVH_BAD_INDEX) return fail(VRHIP_ERR_INVALID, "a triangle index is >= n_verts");
+    if (st.flags & vr::DEVBVH_NONFINITE) return fail(VRHIP_ERR_INVALID, "a referenced vertex position is not finite");
+    if (st.depth != sh.depth || st.nodes != sh.nodes || st.leaves != sh.leaves || st.depth > 62)
+        return fail(VRHIP_ERR_BVH, "device BVH build: the tree is not the shape its size gives");
+    dfree(c->bvh); dfree(c->bvh16); dfree(c->verts); dfree(c->tri_e); dfree(c->tpath);
+    dfree(c->normals); dfree(c->tangents); dfree(c->uvs);
+    c->bvh = b.o.bvh; c->bvh16 = b.o.bvh16; c->verts = b.o.verts; c->tri_e = b.o.tri_e; c->tpath = b.o.tpath;
+    c->normals = b.o.normals; c->tangents = b.o.tangents; c->uvs = b.o.uvs;
+    b.o = vr::DevBuildOut{};
+    c->n_bvh = 4 * (size_t)st.nodes; c->n_slots = st.slots;
+    c->bvh_depth = st.depth; c->bvh_nodes = st.nodes;
+    c->dev_nodes = st.nodes;
+    c->dev_tris = sh.n_refs;
+    c->mesh = true;
+    return VRHIP_OK;
+}
+
+// The resident mesh back in the reference layout: the LIFO flatten of
+// vr::build_flat over the device tree, so the result does not depend on the
+// device's node order.
+int vrhip_export_mesh_flat(vrhip_ctx* c, float* bvh, size_t* n_bvh_f4, float* verts, float* normals, float* tangents,
+                           float* uvs, size_t* n_slots)
+{
+    if (!c) return fail(VRHIP_ERR_INVALID, "null ctx");
+    if (!n_bvh_f4 || !n_slots) return fail(VRHIP_ERR_INVALID, "size outputs are required");
+    if (!c->mesh || c->dev_nodes == 0) return fail(VRHIP_ERR_INVALID, "no mesh loaded");
+    int rc = set_device(c); if (rc) return rc;
+    if ((rc = svc_close(c)) != VRHIP_OK) return rc;
+    const size_t nv = 3 * (size_t)c->dev_tris;
+    std::vector<vr4> dn(4 * (size_t)c->dev_nodes), dnrm(nv), dtan(nv);
+    std::vector<vr3> dv(nv);
+    std::vector<vr2> duv(nv);
+    HIP_TRY(hipMemcpyAsync(dn.data(), c->bvh, dn.size() * 16, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(dv.data(), c->verts, nv * sizeof(vr3), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(dnrm.data(), c->normals, nv * 16, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(dtan.data(), c->tangents, nv * 16, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(duv.data(), c->uvs, nv * 8, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    if ((rc = svc_verify(c)) != VRHIP_OK) return rc;
+
+    std::vector<vr4> ob(4, vr4{ 0.f, 0.f, 0.f, 0.f }), ov, on, ot;
+    std::vector<vr2> ou;
+    ov.reserve(nv + nv / 3); on.reserve(nv + nv / 3); ot.reserve(nv + nv / 3); ou.reserve(nv + nv / 3);
+    uint32_t tb;
+    const int32_t tbits = (int32_t)0x80000000;
+    std::memcpy(&tb, &tbits, 4);
+    float term;
+    std::memcpy(&term, &tb, 4);
+    std::vector<std::pair<size_t, size_t>> stack{ { 0, 0 } };   // (device node, output float4 offset)
+    while (!stack.empty()) {
+        const size_t node = stack.back().first, idx = stack.back().second;
+        stack.pop_back();
+        int32_t indices[2];
+        for (int i = 0; i < 2; ++i) {
+            int32_t ci;
+            std::memcpy(&ci, &dn[4 * node + 3].x + i, 4);
+            if (ci >= 0) {
+                if ((size_t)ci / 4 >= c->dev_nodes || ob.size() > dn.size()) return fail(VRHIP_ERR_BVH, "resident tree is malformed");
+                indices[i] = (int32_t)ob.size();
+                stack.push_back({ (size_t)ci / 4, ob.size() });
+                ob.resize(ob.size() + 4, vr4{ 0.f, 0.f, 0.f, 0.f });
+                continue;
+            }
+            const uint32_t code = (uint32_t)~ci;
+            const size_t first = code >> kLeafCountBits, count = code & ((1u << kLeafCountBits) - 1u);
+            if (first + count > c->dev_tris) return fail(VRHIP_ERR_BVH, "resident tree is malformed");
+            indices[i] = ~(int32_t)ov.size();
+            for (size_t s = 3 * first; s < 3 * (first + count); ++s) {
+                ov.push_back(vr4{ dv[s].x, dv[s].y, dv[s].z, 0.f });
+                on.push_back(dnrm[s]);
+                ot.push_back(dtan[s]);
+                ou.push_back(duv[s]);
+            }
+            ov.push_back(vr4{ term, 0.f, 0.f, 0.f });
+            ot.push_back(vr4{ term, 0.f, 0.f, 0.f });
+            on.push_back(vr4{ term, 0.f, 0.f, 0.f });
+            ou.push_back(vr2{ term, 0.f });
+        }
+        ob[idx + 0] = dn[4 * node + 0];
+        ob[idx + 1] = dn[4 * node + 1];
+        ob[idx + 2] = dn[4 * node + 2];
+        float f0, f1;
+        std::memcpy(&f0, &indices[0], 4);
+        std::memcpy(&f1, &indices[1], 4);
+        ob[idx + 3] = vr4{ f0, f1, 0.f, 0.f };
+    }
+    if (bvh && verts && normals && tangents && uvs) {
+        if (*n_bvh_f4 < ob.size() || *n_slots < ov.size()) return fail(VRHIP_ERR_INVALID, "output arrays too small");
+        std::memcpy(bvh, ob.data(), ob.size() * 16);
+        std::memcpy(verts, ov.data(), ov.size() * 16);
+        std::memcpy(normals, on.data(), on.size() * 16);
+        std::memcpy(tangents, ot.data(), ot.size() * 16);
+        std::memcpy(uvs, ou.data(), ou.size() * 8);
+    }
+    *n_bvh_f4 = ob.size();
+    *n_slots = ov.size();
+    return VRHIP_OK;
 }
 
 #ifndef VR_SERVICE_HDRI_FRAMES
@@ -2302,6 +2451,23 @@ int vrhip_selftest_math(int device, int fn, const float* a, const float* b, floa
     if (e) return fail(VRHIP_ERR_HIP, "selftest launch failed");
     HIP_TRY(hipMemcpy(out, dout, n * 4, hipMemcpyDeviceToHost));
     (void)hipFree(da); (void)hipFree(db); (void)hipFree(dout);
+    return VRHIP_OK;
+}
+
+int vrhip_selftest_half_box(int device, const float* in, size_t n, uint16_t* down, uint16_t* up)
+{
+    if (!in || !down || !up) return fail(VRHIP_ERR_INVALID, "null argument");
+    HIP_TRY(hipSetDevice(device));
+    float* din = nullptr;
+    uint16_t* dout = nullptr;                             // down, then up
+    HIP_TRY(hipMalloc((void**)&din, n * 4 + 4));
+    if (hipMalloc((void**)&dout, n * 4 + 4) != hipSuccess) { (void)hipFree(din); return fail(VRHIP_ERR_NOMEM, "selftest buffers"); }
+    hipError_t e = hipMemcpy(din, in, n * 4, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = (hipError_t)vr::launch_half_box(din, n, dout, dout + n, nullptr);
+    if (e == hipSuccess) e = hipMemcpy(down, dout, n * 2, hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = hipMemcpy(up, dout + n, n * 2, hipMemcpyDeviceToHost);
+    (void)hipFree(din); (void)hipFree(dout);
+    if (e != hipSuccess) return fail(VRHIP_ERR_HIP, std::string("half box selftest: ") + hipGetErrorString(e));
     return VRHIP_OK;
 }
 

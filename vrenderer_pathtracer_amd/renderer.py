@@ -232,6 +232,65 @@ class VRendererHIP:
                                                fptr(arrs["tangents"]), fptr(arrs["uvs"]),
                                                arrs["verts"].size // 4), "vrhip_upload_mesh_flat")
 
+    def initMeshDevice(self, positions, tris, normals=None, tangents=None, uvs=None, max_leaf_tris: int = 2) -> None:
+        """Build the mesh BVH on the GPU from torch tensors that live on the
+        renderer's device (vrhip_upload_mesh_device): positions, normals,
+        tangents (N,3) float32, uvs (N,2) float32, tris (M,3) int32 or uint32,
+        all contiguous; the optional arrays default to zeros.  ValueError for
+        a wrong device, dtype or layout.  Synchronises torch's current stream
+        on that device first (the build runs on the renderer's own stream)."""
+        import torch
+        self._need_ctx()
+        if isinstance(self._device, (list, tuple)):
+            dev = int(self._device[0])
+        else:
+            dev = int(self._device)
+        int_types = tuple(t for t in (torch.int32, getattr(torch, "uint32", None)) if t is not None)
+
+        def ptr(name, t, cols, dtypes, rows=None):
+            if t is None:
+                return None
+            if not isinstance(t, torch.Tensor):
+                raise ValueError(f"{name}: expected a torch tensor")
+            if t.device.type != "cuda" or t.device.index != dev:
+                raise ValueError(f"{name}: tensor is on {t.device}, the renderer on GPU {dev}")
+            if t.dtype not in dtypes:
+                raise ValueError(f"{name}: dtype {t.dtype} (expected {' or '.join(str(d) for d in dtypes)})")
+            if t.dim() != 2 or t.shape[1] != cols or (rows is not None and t.shape[0] != rows):
+                raise ValueError(f"{name}: shape {tuple(t.shape)} (expected ({'N' if rows is None else rows}, {cols}))")
+            if not t.is_contiguous():
+                raise ValueError(f"{name}: tensor is not contiguous")
+            return ctypes.c_void_p(t.data_ptr())
+
+        p_pos = ptr("positions", positions, 3, (torch.float32,))
+        p_tri = ptr("tris", tris, 3, int_types)
+        if p_pos is None or p_tri is None:
+            raise ValueError("positions and tris are required")
+        nv, nt = int(positions.shape[0]), int(tris.shape[0])
+        p_nrm = ptr("normals", normals, 3, (torch.float32,), nv)
+        p_tan = ptr("tangents", tangents, 3, (torch.float32,), nv)
+        p_uvs = ptr("uvs", uvs, 2, (torch.float32,), nv)
+        torch.cuda.current_stream(dev).synchronize()
+        check(self._lib.vrhip_upload_mesh_device(self._ctx, p_pos, p_nrm, p_tan, p_uvs, nv, p_tri, nt,
+                                                 int(max_leaf_tris)), "vrhip_upload_mesh_device")
+
+    def export_mesh_flat(self) -> dict:
+        """The resident mesh in the reference layout (vrhip_export_mesh_flat):
+        the dict build_flat returns, whichever call uploaded the mesh."""
+        n_bvh = ctypes.c_size_t(0)
+        n_slots = ctypes.c_size_t(0)
+        check(self._lib.vrhip_export_mesh_flat(self._need_ctx(), None, ctypes.byref(n_bvh), None, None, None, None,
+                                               ctypes.byref(n_slots)), "vrhip_export_mesh_flat(size)")
+        out = {"bvh": np.zeros((n_bvh.value, 4), np.float32),
+               "verts": np.zeros((n_slots.value, 4), np.float32),
+               "normals": np.zeros((n_slots.value, 4), np.float32),
+               "tangents": np.zeros((n_slots.value, 4), np.float32),
+               "uvs": np.zeros((n_slots.value, 2), np.float32)}
+        check(self._lib.vrhip_export_mesh_flat(self._ctx, fptr(out["bvh"]), ctypes.byref(n_bvh), fptr(out["verts"]),
+                                               fptr(out["normals"]), fptr(out["tangents"]), fptr(out["uvs"]),
+                                               ctypes.byref(n_slots)), "vrhip_export_mesh_flat")
+        return out
+
     def loadHDR(self, pixels, w: int = None, h: int = None) -> None:
         """pixels: float32 (H,W,4) or float16 (H,W,4) (Imf::Rgba layout)."""
         self._need_ctx()
@@ -510,6 +569,17 @@ def selftest_math(fn: int, a, b=None, device: int = 0) -> np.ndarray:
     out = np.zeros_like(a)
     check(_native.lib().vrhip_selftest_math(device, fn, fptr(a), fptr(b), fptr(out), a.size), "vrhip_selftest_math")
     return out
+
+
+def selftest_half_box(values, device: int = 0):
+    """The device BVH builder's outward fp32 -> fp16 box rounding
+    (vrhip_selftest_half_box): (down, up) as uint16 bit patterns."""
+    a = _f32(values).reshape(-1)
+    down = np.zeros(a.size, np.uint16)
+    up = np.zeros(a.size, np.uint16)
+    check(_native.lib().vrhip_selftest_half_box(device, fptr(a), a.size, down.ctypes.data_as(_native._u16),
+                                                up.ctypes.data_as(_native._u16)), "vrhip_selftest_half_box")
+    return down, up
 
 
 def selftest_rcp(lo_bits: int, hi_bits: int, device: int = 0):
