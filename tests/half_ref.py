@@ -6,7 +6,7 @@ import numpy as np
 
 def half_reference(x, up):
     """np.float16(x), stepped one half ulp outward where it lies on the wrong
-    side of x.  Reproduces half_bits_directed (vrhip_api.cpp) on the values
+    side of x.  Reproduces half_bits_directed (vr_mesh_layout.cpp) on the values
     below: checked with a stand-alone host program that calls that function."""
     with np.errstate(over="ignore"):
         h = x.astype(np.float16)

@@ -2,7 +2,9 @@
 // driver for the host code of libvrhip.so that parses untrusted input
 // (SURVEY.md §5): the OpenEXR reader (vr_exr.cpp), the MERL reader
 // (vr_merl.cpp), the BVH builder and the flattened-tree validator
-// (vr_bvh.cpp: vrhip_build_flat / vrhip_validate_flat).  Built and run by
+// (vr_bvh.cpp: vrhip_build_flat / vrhip_validate_flat) and the device mesh
+// layout (vr_mesh_layout.cpp: vrhip_upload_mesh_flat / vrhip_export_mesh_flat).
+// Built and run by
 // tests/test_sanitize.py with -fsanitize=address,undefined
 // -fno-sanitize-recover=all: any report aborts with a non-zero status.
 //
@@ -10,6 +12,8 @@
 //   sanitize_driver merl FILE...
 //   sanitize_driver bvh             degenerate / hostile meshes through the builder
 //   sanitize_driver flat N          N corrupted copies of a built tree through the validator
+//   sanitize_driver layout N        built trees to the device layout and back (byte for byte), then
+//                                   the copies of `flat N` that the validator accepts to the device layout
 //
 // Every call must return (0 or an error code); the driver prints one line
 // "<mode> ok=<accepted> rejected=<rejected>".
@@ -25,6 +29,7 @@
 #include "vr_bvh.hpp"
 #include "vr_exr.hpp"
 #include "vr_merl.hpp"
+#include "vr_mesh_layout.hpp"
 
 namespace {
 
@@ -132,19 +137,27 @@ int run_bvh()
 
 // Corrupted copies of a valid flattened tree, each passed at its exact
 // (claimed) size so that any read past it is a heap overflow ASan reports.
-int run_flat(int n_cases)
-{
+struct FlatCases {
     vr::FlatMesh f;
-    Mesh m = random_mesh(400, 23);
-    if (build(m, (uint32_t)(m.pos.size() / 3), 2, f) != 0) return 2;
-    std::vector<float> bvh0((const float*)f.bvh.data(), (const float*)f.bvh.data() + 4 * f.bvh.size());
-    std::vector<float> verts0((const float*)f.verts.data(), (const float*)f.verts.data() + 4 * f.verts.size());
-    const size_t nb = bvh0.size() / 4, ns = verts0.size() / 4;   // float4 counts
-    Lcg r(29);
-    int ok = 0, rejected = 0;
-    for (int c = 0; c < n_cases; ++c) {
+    std::vector<float> bvh0, verts0;
+    size_t nb = 0, ns = 0;                          // float4 counts
+    Lcg r{ 29 };
+    std::vector<float> b, v;                        // the current case, exact size
+    size_t nbc = 0, nsc = 0;
+
+    bool init()
+    {
+        Mesh m = random_mesh(400, 23);
+        if (build(m, (uint32_t)(m.pos.size() / 3), 2, f) != 0) return false;
+        bvh0.assign((const float*)f.bvh.data(), (const float*)f.bvh.data() + 4 * f.bvh.size());
+        verts0.assign((const float*)f.verts.data(), (const float*)f.verts.data() + 4 * f.verts.size());
+        nb = bvh0.size() / 4; ns = verts0.size() / 4;
+        return true;
+    }
+    void next()
+    {
         std::vector<float> bvh = bvh0, verts = verts0;
-        size_t nbc = nb, nsc = ns;
+        nbc = nb; nsc = ns;
         const int kind = (int)(r.next() % 8u);
         auto as_float = [](int32_t i) { float v; std::memcpy(&v, &i, 4); return v; };
         switch (kind) {
@@ -177,14 +190,121 @@ int run_flat(int n_cases)
             bvh[16 * node + 12] = as_float(~(int32_t)(ns + (r.next() % 64u))); break;
         }
         }
-        // exact-size copies: the validator may read nothing past them
-        std::vector<float> b(bvh.begin(), bvh.begin() + 4 * nbc), v(verts.begin(), verts.begin() + 4 * nsc);
+        // exact-size copies: the code under test may read nothing past them
+        b.assign(bvh.begin(), bvh.begin() + 4 * nbc);
+        v.assign(verts.begin(), verts.begin() + 4 * nsc);
+    }
+    int validate() const
+    {
         uint32_t d = 0, n = 0;
-        const int rc = vr::validate_flat(b.empty() ? nullptr : b.data(), nbc, v.empty() ? nullptr : v.data(), nsc,
-                                         &d, &n);
-        (rc == 0 ? ok : rejected)++;
+        return vr::validate_flat(b.empty() ? nullptr : b.data(), nbc, v.empty() ? nullptr : v.data(), nsc, &d, &n);
+    }
+};
+
+int run_flat(int n_cases)
+{
+    FlatCases fc;
+    if (!fc.init()) return 2;
+    int ok = 0, rejected = 0;
+    for (int c = 0; c < n_cases; ++c) {
+        fc.next();
+        (fc.validate() == 0 ? ok : rejected)++;
     }
     std::printf("flat ok=%d rejected=%d\n", ok, rejected);
+    return 0;
+}
+
+// build_flat -> to_device_layout -> device_to_flat gives build_flat's five
+// arrays back byte for byte.  1: round trip exact, 0: refused with a reason, -1: failure.
+int layout_round_trip(const vr::FlatMesh& f)
+{
+    vr::DeviceMesh dm;
+    std::string why;
+    if (!vr::to_device_layout(&f.bvh[0].x, f.bvh.size(), f.verts.data(), f.normals.data(), f.tangents.data(),
+                              f.uvs.data(), dm, why))
+        return why.empty() ? -1 : 0;
+    vr::FlatMesh g;
+    if (!vr::device_to_flat(dm.nodes, dm.tris, dm.normals, dm.tangents, dm.uvs, g)) return -1;
+    auto same = [](const auto& a, const auto& b) {
+        return a.size() == b.size() && std::memcmp(a.data(), b.data(), a.size() * sizeof(a[0])) == 0;
+    };
+    return same(f.bvh, g.bvh) && same(f.verts, g.verts) && same(f.normals, g.normals) &&
+                   same(f.tangents, g.tangents) && same(f.uvs, g.uvs) ? 1 : -1;
+}
+
+// Part 1: the meshes of run_bvh that build, a single triangle and a tree with
+// more inner nodes than the area-ordered prefix (VR_TOP_NODES = 1024) through
+// the round trip.  Part 2: the corrupted arrays of run_flat that validate_flat
+// accepts (what vrhip_upload_mesh_flat lets through) to the device layout, the
+// attribute arrays cut to the same exact size.  Prints the validator-accepted
+// count as ok= and the rest as rejected=.
+int run_layout(int n_cases)
+{
+    const float inf = std::numeric_limits<float>::infinity(), nan = std::numeric_limits<float>::quiet_NaN();
+    int trips = 0;
+    auto trip = [&](const Mesh& m, uint32_t n_verts, uint32_t leaf, bool must, bool attrs = true) {
+        vr::FlatMesh f;
+        if (build(m, n_verts, leaf, f, attrs) != 0) return !must;
+        const int t = layout_round_trip(f);
+        if (t < 0 || (must && t == 0)) { std::fprintf(stderr, "layout round trip failed (%d)\n", t); return false; }
+        trips += t;
+        return true;
+    };
+    for (uint32_t leaf : { 0u, 1u, 2u, 8u }) {
+        Mesh m = random_mesh(300, 1 + leaf);
+        if (!trip(m, (uint32_t)(m.pos.size() / 3), leaf, true)) return 2;
+        if (!trip(m, (uint32_t)(m.pos.size() / 3), leaf, true, false)) return 2;
+        Mesh one = random_mesh(1, 7);
+        if (!trip(one, 3, leaf, true)) return 2;
+        Mesh same = random_mesh(500, 9);
+        for (size_t i = 0; i < same.pos.size(); ++i) same.pos[i] = 1.f;
+        if (!trip(same, (uint32_t)(same.pos.size() / 3), leaf, false)) return 2;
+        Mesh dup = random_mesh(1, 11);
+        for (int k = 0; k < 1999; ++k) dup.tris.insert(dup.tris.end(), { 0u, 1u, 2u });
+        if (!trip(dup, 3, leaf, false)) return 2;
+        Mesh line = random_mesh(200, 13);
+        for (size_t v = 0; v < line.pos.size() / 3; ++v) { line.pos[3 * v + 1] = 0.f; line.pos[3 * v + 2] = 0.f; }
+        if (!trip(line, (uint32_t)(line.pos.size() / 3), leaf, false)) return 2;
+        for (float bad : { nan, inf, -inf, 3.0e38f, -3.0e38f, 1e-38f }) {
+            Mesh h = random_mesh(64, 17);
+            for (size_t i = 0; i < h.pos.size(); i += 7) h.pos[i] = bad;
+            if (!trip(h, (uint32_t)(h.pos.size() / 3), leaf, false)) return 2;
+            for (size_t i = 0; i < h.pos.size(); ++i) h.pos[i] = bad;
+            if (!trip(h, (uint32_t)(h.pos.size() / 3), leaf, false)) return 2;
+        }
+    }
+    {
+        Mesh big = random_mesh(3000, 31);                                       // past the area-ordered prefix
+        vr::FlatMesh f;
+        uint32_t d = 0, n = 0;
+        if (build(big, (uint32_t)(big.pos.size() / 3), 2, f) != 0 ||
+            vr::validate_flat(&f.bvh[0].x, f.bvh.size(), &f.verts[0].x, f.verts.size(), &d, &n) != 0 || n <= 1024u) {
+            std::fprintf(stderr, "the large mesh has %u inner nodes, wanted more than 1024\n", n);
+            return 2;
+        }
+        if (layout_round_trip(f) != 1) { std::fprintf(stderr, "large mesh round trip failed\n"); return 2; }
+        ++trips;
+    }
+    FlatCases fc;
+    if (!fc.init()) return 2;
+    int ok = 0, rejected = 0, laid = 0, refused = 0;
+    for (int c = 0; c < n_cases; ++c) {
+        fc.next();
+        if (fc.validate() != 0) { ++rejected; continue; }
+        ++ok;
+        const std::vector<vr::vr4> nrm(fc.f.normals.begin(), fc.f.normals.begin() + fc.nsc);
+        const std::vector<vr::vr4> tan(fc.f.tangents.begin(), fc.f.tangents.begin() + fc.nsc);
+        const std::vector<vr::vr2> uv(fc.f.uvs.begin(), fc.f.uvs.begin() + fc.nsc);
+        vr::DeviceMesh dm;
+        std::string why;
+        if (vr::to_device_layout(fc.b.data(), fc.nbc, (const vr::vr4*)fc.v.data(), nrm.data(), tan.data(), uv.data(), dm, why))
+            ++laid;
+        else if (!why.empty())
+            ++refused;
+        else { std::fprintf(stderr, "refused without a reason\n"); return 2; }
+    }
+    std::fprintf(stderr, "layout: %d round trips, %d corrupted arrays laid out, %d refused\n", trips, laid, refused);
+    std::printf("layout ok=%d rejected=%d\n", ok, rejected);
     return 0;
 }
 
@@ -192,11 +312,12 @@ int run_flat(int n_cases)
 
 int main(int argc, char** argv)
 {
-    if (argc < 2) { std::fprintf(stderr, "usage: sanitize_driver exr|merl FILE... | bvh | flat N\n"); return 2; }
+    if (argc < 2) { std::fprintf(stderr, "usage: sanitize_driver exr|merl FILE... | bvh | flat N | layout N\n"); return 2; }
     const std::string mode = argv[1];
     if (mode == "exr" || mode == "merl") return run_files(mode == "exr", argc, argv);
     if (mode == "bvh") return run_bvh();
     if (mode == "flat") return run_flat(argc > 2 ? std::atoi(argv[2]) : 2000);
+    if (mode == "layout") return run_layout(argc > 2 ? std::atoi(argv[2]) : 2000);
     std::fprintf(stderr, "unknown mode %s\n", mode.c_str());
     return 2;
 }

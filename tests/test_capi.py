@@ -158,7 +158,7 @@ def test_validate_flat_rejects_corruption(native):
 
 def test_validate_flat_rejects_shared_nodes_and_leaves(native):
     """The device layout keys the equal-t tie-break on each triangle's unique
-    root path (vrhip_api.cpp tri_paths), so the flattened BVH must be a tree
+    root path (vr_mesh_layout.cpp tri_paths), so the flattened BVH must be a tree
     (the reference's LIFO flatten always is, src/vRendererCuda.cpp:204-279):
     an inner node or a leaf run reached from two parents is rejected before
     upload (vrhip_upload_mesh_flat validates first)."""

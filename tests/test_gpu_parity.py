@@ -683,7 +683,7 @@ def test_longest_first_order_is_scheduling_only(native, oracle, cfg, tiling, ove
     Consecutive one-frame calls -- the second and later ones ordered, on one
     path stream or on three -- equal the band-order render bit for bit, and
     the oracle.  320x224 has 1,120 sub-tiles, more than 8 XCDs x
-    VR_XCD_BANDS = 1,024: the order lists' second band (g >= 1 in grab's
+    kXcdBands = 1,024: the order lists' second band (g >= 1 in grab's
     lookup, every 720p and 4K one-frame launch) is exercised too."""
     w, h = size
     sc = scenes.make_scene(cfg, w, h) if cfg != "C5" else scenes.make_scene("C5", w, h, knot=(150, 75))

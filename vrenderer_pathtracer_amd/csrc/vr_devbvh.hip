@@ -30,7 +30,6 @@ namespace vr {
 namespace {
 
 constexpr int kBlock = 256;                       // four wave64
-constexpr int kLeafCountBits = 7;                 // as vrhip_api.cpp / vr_kernel.hpp
 
 struct Box { float4 lo, hi; };                    // .w unused: two 16-B accesses per box
 

@@ -1,6 +1,6 @@
 // vr_devbvh.hpp -- the device BVH builder (vr_devbvh.hip): a Morton-ordered,
 // count-balanced tree built from device-resident triangles straight into the
-// eight arrays of the device mesh layout (vrhip_api.cpp DeviceMesh).  No
+// eight arrays of the device mesh layout (vr_mesh_layout.hpp DeviceMesh).  No
 // reference counterpart: the reference builds on the host (src/SBVH.cpp).
 #pragma once
 #include <cstddef>
@@ -17,8 +17,9 @@ namespace vr {
 #endif
 
 // IEEE binary16 bits of the float with bit pattern `bits`, rounded toward
-// +inf (up) or -inf (down); equals half_bits_directed (vrhip_api.cpp) for
-// every finite float.  The magnitude is truncated toward zero and stepped one
+// +inf (up) or -inf (down); equals half_bits_directed (vr_mesh_layout.cpp) for
+// every non-NaN float (both infinities included; NaN patterns differ, see
+// docs/DESIGN_HISTORY.md).  The magnitude is truncated toward zero and stepped one
 // half ulp outward when that moved it to the wrong side: 0x7bff + 1 is
 // infinity (out of range on the outward side), 0x03ff + 1 the smallest normal.
 VR_DEVBVH_HD inline uint16_t half_directed(uint32_t bits, bool up)

@@ -19,10 +19,10 @@ namespace vr {
 // sync_flag): every wave waits for its stores to complete, the block's
 // arrival is counted, and the last block to arrive stores the call's number
 // to host-coherent memory at system scope -- the host sees the frame done
-// without waiting for the stream's completion signal (vrhip_api.cpp one_sync).
+// without waiting for the stream's completion signal (vrhip_render.cpp one_sync).
 // The results are then complete in the L2s; the end of the kernel writes them
 // back before any later work on the stream starts, and the library arms the
-// flag only on a stream no other party queues work on (vrhip_api.cpp).  (An
+// flag only on a stream no other party queues work on (vrhip_render.cpp).  (An
 // agent-scope release per wave -- an L2 write-back each -- cost 360 us per
 // 1280x720 finish pass, r06zr.)
 __device__ __forceinline__ void finish_arrive(const RenderParams& p)
@@ -48,12 +48,8 @@ __device__ __forceinline__ void finish_arrive(const RenderParams& p)
 }
 
 __device__ __forceinline__ void finish_body(const RenderParams& p, const float* T);
-#ifndef VR_FINISH_LDS_TONE
-#define VR_FINISH_LDS_TONE 1
-#endif
 __global__ void __launch_bounds__(kBlockThreads) finish_kernel(const RenderParams p)
 {
-#if VR_FINISH_LDS_TONE
     // the tonemap's 256 thresholds in LDS: the dependent table reads of each
     // colour byte (tone_byte) then wait on LDS instead of the L1
     static_assert(kBlockThreads == 256, "one threshold per thread");
@@ -61,9 +57,6 @@ __global__ void __launch_bounds__(kBlockThreads) finish_kernel(const RenderParam
     T[threadIdx.x] = p.tone_t ? p.tone_t[threadIdx.x] : 0.f;
     __syncthreads();
     finish_body(p, p.tone_t ? T : nullptr);
-#else
-    finish_body(p, p.tone_t);
-#endif
     if (p.sync_flag) finish_arrive(p);
 }
 
@@ -132,7 +125,7 @@ __device__ __forceinline__ void finish_body(const RenderParams& p, const float* 
 
 // Longest-first order of a launch's sub-tiles for the next launch on the
 // same scratch (RenderParams::sub_order): block x sorts the sub-tiles XCD x's
-// queues serve (bands of VR_XCD_BANDS, dealt round-robin to the 8 XCDs) by
+// queues serve (bands of kXcdBands, dealt round-robin to the 8 XCDs) by
 // the cost this launch measured (sub_cost, written by finish_kernel: node
 // visits of all their paths), most expensive first, by a counting sort over
 // half-octave cost classes.  Scheduling only: any permutation renders the
@@ -152,7 +145,7 @@ __global__ void __launch_bounds__(256) order_kernel(const uint32_t* __restrict__
 {
     __shared__ uint32_t hist[kCostClasses];
     const uint32_t x = blockIdx.x, tid = threadIdx.x;
-    constexpr uint32_t B = (uint32_t)VR_XCD_BANDS;
+    constexpr uint32_t B = kXcdBands;
     auto sub_of = [&](uint32_t k) { return ((k / B) * 8u + x) * B + (k % B); };
     // this XCD's sub-tiles: k < n_x  <=>  sub_of(k) < n_sub
     const uint32_t full = n_sub / (8u * B), rem = n_sub - full * 8u * B;

@@ -201,7 +201,7 @@ __device__ __forceinline__ vr4 sphere_normal(const HitRec& hr, const Ray& r) {
     return normalize4(sub4(hp, mk4(s.px, s.py, s.pz, 0.f)));
 }
 
-// Device mesh layout (built from the reference layout at upload, vrhip_api.cpp):
+// Device mesh layout (built from the reference layout at upload, vr_mesh_layout.cpp):
 //   nodes: the reference's 4 x float4 per inner node, except that a leaf
 //          child is ~((first_tri << 7) | tri_count) into the compact arrays;
 //   tris:  3 float4 vertex positions per triangle, leaves contiguous, in the
@@ -209,8 +209,7 @@ __device__ __forceinline__ vr4 sphere_normal(const HitRec& hr, const Ray& r) {
 //   attributes (normals, tangents, uvs): same indexing, fetched only for the
 //          final hit of a ray.
 // The triangles tested and their order are those of the reference layout, so
-// the closest hit (ties included) is unchanged.
-constexpr int kLeafCountBits = 7;
+// the closest hit (ties included) is unchanged.  (kLeafCountBits: vr_params.hpp)
 
 // Per-block LDS: the traversal stacks (entry-major, one column per thread)
 // and a copy of the first nodes of the area-ordered node array (rows 0-2 and
@@ -275,11 +274,8 @@ struct Trav {
 // whole walk (C2 +0.5 %, C5 +0.5 %) -- except in the small-launch kernels,
 // whose helper lanes cull with the smaller of their own and their owner's
 // (help_step).
-#ifndef VR_TCULL_KEPT
-#define VR_TCULL_KEPT 0           // 1: every kernel keeps tcull in a register (A/B builds)
-#endif
 template <uint32_t FEAT>
-constexpr bool tcull_kept() { return VR_TCULL_KEPT != 0 || (FEAT & F_SMALL) != 0u; }
+constexpr bool tcull_kept() { return (FEAT & F_SMALL) != 0u; }
 
 template <uint32_t FEAT>
 __device__ __forceinline__ void trav_init(const RenderParams& p, const Ray& r, float t0, Trav& tr, const Lds& L)
@@ -317,22 +313,6 @@ __device__ __forceinline__ int trav_pop(Trav& tr, const Lds& L)
     return L.stk[(tr.sp--) * L.stride];
 }
 
-// Whether node visits may read the block's LDS copy of the tree top.  Off
-// (VR_SVC_LDS_NODES=0, A/B builds) in the Cornell-box service kernels: the
-// wave-uniform choice almost never finds a diverged wave entirely in the
-// cached top there (0.2 % of node bytes, r05), so the test per visit is spent
-// for nothing.
-#ifndef VR_SVC_LDS_NODES
-#define VR_SVC_LDS_NODES 1
-#endif
-#ifndef VR_LDS_PER_LANE
-#define VR_LDS_PER_LANE 0
-#endif
-template <uint32_t FEAT>
-constexpr bool lds_nodes_on() {
-    return VR_SVC_LDS_NODES != 0 || (FEAT & F_SERVICE) == 0u || (FEAT & F_CORNELL) == 0u;
-}
-
 // One inner-node visit (:295-343): fetch (LDS copy or L2/HBM), two slab
 // tests, near child next, far child pushed when both are entered, pop when
 // neither is.  Leaves in tr.nodeAddr are left to the caller.
@@ -348,9 +328,8 @@ __device__ __forceinline__ void node_step(const RenderParams& p, const Ray& r, T
     int idx0, idx1;
     const int node = tr.nodeAddr >> 2;
     // wave-uniform choice between the LDS copy and L2/HBM: a diverged wave
-    // would pay both round trips (VR_LDS_PER_LANE=1: each lane on its own)
-    const bool in_lds = lds_nodes_on<FEAT>() &&
-                        (VR_LDS_PER_LANE ? node < L.n_cached : __ballot(node >= L.n_cached) == 0ull);
+    // would pay both round trips
+    const bool in_lds = __ballot(node >= L.n_cached) == 0ull;
     if (COUNT) {
         cnt.nodes_lds += in_lds ? 1u : 0u;
         if (!in_lds) { cnt.ld128 += strict ? 3u : 2u; cnt.ld64 += strict ? 1u : 0u; }
@@ -431,27 +410,6 @@ __device__ __forceinline__ void node_step(const RenderParams& p, const Ray& r, T
     if (both) stk[(tr.sp + 1) * L.stride] = farc;
     tr.sp += both ? 1 : (none ? -1 : 0);
     tr.nodeAddr = none ? top : nearc;
-}
-
-// The root visit at ray setup (path kernels).  Every lane that starts a walk
-// is at the root, so node_step's wave-uniform choice takes the block's LDS
-// copy of the tree top: the walk's first visit -- the same fetch of the same
-// node, the same slab tests, the same push and pop -- without the two global
-// loads and the round trip it cost inside trav_iter, and a ray that enters
-// neither child of the root (most Cornell-box bounce rays run wall to wall
-// past the mesh) leaves for shading at once instead of passing through the
-// traversal state machine.  The walk then resumes from the root's near child
-// exactly as it would have, so every lane's sequence of visits and tests is
-// unchanged.  false: the walk is over (no mesh hit).
-#ifndef VR_ROOT_AT_SETUP
-#define VR_ROOT_AT_SETUP 0
-#endif
-template <bool COUNT, uint32_t FEAT>
-__device__ __forceinline__ bool root_visit(const RenderParams& p, const Ray& r, Trav& tr, const Lds& L, Cnt& cnt)
-{
-    if (VR_ROOT_AT_SETUP == 0 || L.n_cached < 1) return true;
-    node_step<COUNT, FEAT>(p, r, tr, L, cnt);
-    return tr.nodeAddr != kSentinel;
 }
 
 // Equal-t tie-break of the culled traversal.  The reference keeps the first
@@ -575,17 +533,10 @@ constexpr int node_break() {
 // ~200 node visits, ~100 triangle tests) then needed 50-150 outer iterations
 // and ran 300-770 us, the critical path of a one-frame launch (r03 drain
 // diagnostics, removed in r04; git history).
-#ifndef VR_NODE_BREAK_PROP
-#define VR_NODE_BREAK_PROP 1
-#endif
 template <int STACK, bool COUNT, uint32_t FEAT>
 __device__ __forceinline__ void trav_iter(const RenderParams& p, const Ray& r, Trav& tr, const Lds& L, Cnt& cnt)
 {
-#if VR_NODE_BREAK_PROP
     const int brk = node_break<FEAT>() * __popcll(__ballot(1));  // exit when searching * 64 <= brk
-#else
-    const int brk = node_break<FEAT>() * 64;
-#endif
     int leafAddr = 0;
     if (tr.nodeAddr < 0) {                                      // a leaf to start with (a helper's subtree)
         leafAddr = tr.nodeAddr;
@@ -705,13 +656,8 @@ __device__ __forceinline__ bool intersect_scene(const RenderParams& p, const Ray
 // Face normals from the traversal's triangle edges (fill_hit): on in every
 // kernel but the Cornell-box one-frame kernels, which spill 2 VGPRs with it
 // (C2 16-frame steps +0.7 %, C5 one frame per call -1 %, r05s)
-#ifndef VR_FACE_FROM_EDGES
-#define VR_FACE_FROM_EDGES 1
-#endif
 template <uint32_t FEAT>
-constexpr bool face_from_edges() {
-    return VR_FACE_FROM_EDGES != 0 && !((FEAT & F_INLINE_PRIM) != 0u && (FEAT & F_CORNELL) != 0u);
-}
+constexpr bool face_from_edges() { return !((FEAT & F_INLINE_PRIM) != 0u && (FEAT & F_CORNELL) != 0u); }
 template <uint32_t FEAT>
 __device__ __forceinline__ void fill_hit(const RenderParams& p, const Ray& r, const HitRec& hr, Hit& h)
 {
@@ -1042,18 +988,10 @@ __device__ __forceinline__ bool bounce_step(const RenderParams& p, Ray& ray, con
 #ifndef VR_SPEC_SAMPLE
 #define VR_SPEC_SAMPLE 2
 #endif
-#ifndef VR_SPEC_HDRI_SVC
-#define VR_SPEC_HDRI_SVC 0
-#endif
-// (also measured, off: the HDRI service kernels -- C3 -0.4 %, C5 +0.3 %,
-// noise -- and the Cornell whole-frame kernel: ±0, r05v)
-#ifndef VR_SPEC_WHOLE
-#define VR_SPEC_WHOLE 0
-#endif
+    // (also measured, off: the HDRI service kernels -- C3 -0.4 %, C5 +0.3 %,
+    // noise -- and the Cornell whole-frame kernel: ±0, r05v)
     constexpr bool SPEC = VR_SPEC_SAMPLE != 0 && !ref_alg<COUNT, FEAT>() && (FEAT & (F_BRDF | F_VIEW_BRDF)) == 0u &&
-                          (((FEAT & F_CORNELL) != 0u &&
-                            ((FEAT & (F_SERVICE | F_INLINE_PRIM)) != 0u || (VR_SPEC_WHOLE != 0 && (FEAT & F_SMALL) == 0u))) ||
-                           (VR_SPEC_HDRI_SVC != 0 && (FEAT & F_SERVICE) != 0u));
+                          (FEAT & F_CORNELL) != 0u && (FEAT & (F_SERVICE | F_INLINE_PRIM)) != 0u;
     Rng srng = ps.rng;
     float su0 = 0.f, srand2s = 0.f, srand1m = 0.f, ssn = 0.f, scs = 0.f;
     auto spec_sample = [&]() {
@@ -1457,25 +1395,10 @@ constexpr bool prim_has_dir() { return (FEAT & F_EXAMPLE) == 0; }
 // 7-wave C2 kernel's only VGPR spills are vector copies of it (two scratch
 // stores per wave in the prologue, two reloads per refill: ~4 MB of the
 // launch's 996 MiB WRITE_SIZE, so not the write amplification -- DESIGN.md 5).
-// With VR_CAM_RELOAD it is reloaded from the kernel argument segment at the
-// point of use instead: 0 spills, but slower -- C2 -1.0 %, C3 -1.6 %, C5
-// -3.0 % (r04, scripts/ab.py): the allocator's other choices cost more than
-// the reloads did.  Off.
-#ifndef VR_CAM_RELOAD
-#define VR_CAM_RELOAD 0
-#endif
-static_assert(offsetof(RenderParams, cam_o) == 0, "cam_o leads the kernel argument");
-__device__ __forceinline__ vr4 cam_origin(const RenderParams& p)
-{
-#if VR_CAM_RELOAD
-    const vr4* k = (const vr4*)__builtin_amdgcn_kernarg_segment_ptr();
-    asm volatile("" : "+s"(k));                 // opaque: reloaded at every use
-    (void)p;
-    return *k;
-#else
-    return p.cam_o;
-#endif
-}
+// Reloading it from the kernel argument segment at the point of use instead
+// gave 0 spills, but slower -- C2 -1.0 %, C3 -1.6 %, C5 -3.0 % (r04,
+// scripts/ab.py): the allocator's other choices cost more than the reloads did.
+__device__ __forceinline__ vr4 cam_origin(const RenderParams& p) { return p.cam_o; }
 
 // Primary hits, one thread per owned pixel: the camera ray's closest hit
 // (the HitRec intersect_scene returns: t, kind, idx, barycentrics,
@@ -1613,11 +1536,8 @@ enum LaneState : int { LS_SETUP = 0, LS_TRAV = 1, LS_SHADE = 2, LS_DONE = 3, LS_
 // the closest distance is resolved by the reference's own order (ref_first),
 // so the merged hit is the reference's.  Not used by the strict walk, whose
 // exact result relies on the reference's visit order.
-#ifndef VR_HELPERS
-#define VR_HELPERS 1
-#endif
 template <uint32_t FEAT>
-constexpr bool helpers() { return VR_HELPERS != 0 && (FEAT & F_STRICT) == 0u && (FEAT & F_SMALL) != 0u; }
+constexpr bool helpers() { return (FEAT & F_STRICT) == 0u && (FEAT & F_SMALL) != 0u; }
 
 // One wave-synchronous help round: (1) finished helpers hand their closest
 // hit to their owners, one at a time; (2) idle lanes take a subtree each from
@@ -1769,24 +1689,15 @@ constexpr int path_cache_nodes(int stack, int bt, bool c) {
 #ifndef VR_SVC_CORNELL_RES
 #define VR_SVC_CORNELL_RES 1
 #endif
-#ifndef VR_ONEFRAME_CORNELL_RES
-#define VR_ONEFRAME_CORNELL_RES 0    // 1: one-frame Cornell kernels at the 7-wave residency (A/B builds)
-#endif
 template <uint32_t FEAT>
 constexpr bool cornell_kernel() {
     // the one-frame kernels (F_INLINE_PRIM) keep 6 waves: at 7 the interactive
     // C2 rate fell 2,147 -> 2,100 Mpaths/s (r02g); so do the small-launch
     // kernels (F_SMALL), which spilled 19 VGPRs at 7 with helper lanes and
     // cost counting (8-rank C2 shard step 1.317 -> 1.257 ms at 6, r03p)
-    if (VR_ONEFRAME_CORNELL_RES && (FEAT & F_EXACT) != 0u && (FEAT & F_CORNELL) != 0u && (FEAT & F_INLINE_PRIM) != 0u)
-        return true;
     return (FEAT & F_EXACT) != 0u && (FEAT & F_CORNELL) != 0u && (FEAT & F_INLINE_PRIM) == 0u &&
            (FEAT & (F_SMALL | (VR_SVC_CORNELL_RES ? 0u : (uint32_t)F_SERVICE))) == 0u;
 }
-
-#ifndef VR_XCD_BANDS
-#define VR_XCD_BANDS 128
-#endif
 
 template <int STACK, uint32_t FEAT, int BT>
 __device__ __forceinline__ void wave_body(const RenderParams& p, const Lds& L);
@@ -1814,26 +1725,19 @@ __device__ __forceinline__ unsigned long long all_q_of(uint32_t Q) { return Q >=
 // The sub-tile that value v of work-queue head q hands out (>= n_sub: the
 // queue is drained; non-decreasing in v), and the path in `path`.
 // Chunk = (sub-tile, path): the paths of one sub-tile are handed out
-// together.  With VR_XCD_BANDS queue q serves XCD q % 8 (blocks b % 16 == q
-// under round-robin dispatch): bands of VR_XCD_BANDS sub-tiles are dealt
+// together.  Queue q serves XCD q % 8 (blocks b % 16 == q
+// under round-robin dispatch): bands of kXcdBands sub-tiles are dealt
 // round-robin to the XCDs, each XCD's chunks sub-major, alternated between
 // its Q / 8 queues.
 __device__ __forceinline__ uint32_t queue_item(uint32_t q, uint32_t v, uint32_t Q, uint32_t n_paths, uint32_t& path)
 {
-#if VR_XCD_BANDS
     const uint32_t x = q % 8u, h = q / 8u;
     const uint32_t e = v * (Q / 8u) + h;
-    const uint32_t per_band = (uint32_t)VR_XCD_BANDS * n_paths;
+    const uint32_t per_band = kXcdBands * n_paths;
     const uint32_t g = e / per_band, o = e - g * per_band;
     const uint32_t r = o / n_paths;
     path = o - r * n_paths;
-    return (g * 8u + x) * (uint32_t)VR_XCD_BANDS + r;
-#else
-    const uint32_t c = v * Q + q;
-    const uint32_t sb = c / n_paths;
-    path = c - sb * n_paths;
-    return sb;
-#endif
+    return (g * 8u + x) * kXcdBands + r;
 }
 
 // The textured small-launch kernels (C3 shards) keep a path's index in LDS,
@@ -1875,7 +1779,7 @@ __device__ __forceinline__ void wave_body(const RenderParams& p, const Lds& L)
     // out chunks j, j + Q, j + 2Q, ... (one device-scope atomic per chunk; a
     // single head saturates: MI355X_MICROARCH "dequeue").  A wave draws from
     // its block's queue and, once that is drained, from the following ones.
-    // With VR_XCD_BANDS (default 128 sub-tiles = 32 tiles) the sub-tiles are
+    // In bands of kXcdBands (128 sub-tiles = 32 tiles) the sub-tiles are
     // dealt to the 8 XCDs in bands, so each XCD's L2 serves a coherent part of
     // the image (C2 +0.7 %, C3 +1.7 %, C5 +0.7 % over chunk-interleaved queues).
     const uint32_t Q = p.n_queues;                         // power of two, multiple of the 8 XCDs
@@ -1894,15 +1798,13 @@ __device__ __forceinline__ void wave_body(const RenderParams& p, const Lds& L)
             const uint32_t sb = queue_item(qj, __builtin_amdgcn_readfirstlane(v), Q, n_paths, path);
             if (sb < n_sub) {
                 if constexpr (SPARSE) { sub = sb; return; }   // a run of listed pixels
-#if VR_XCD_BANDS
                 // longest-first: the XCD's sub-tiles in the order of the
                 // previous launch's cost (order_kernel); else band order
                 if (p.sub_order) {
-                    const uint32_t x = qj % 8u, r = sb % (uint32_t)VR_XCD_BANDS, g = sb / (8u * (uint32_t)VR_XCD_BANDS);
-                    sub = p.sub_order[x * p.order_cap + g * (uint32_t)VR_XCD_BANDS + r];
+                    const uint32_t x = qj % 8u, r = sb % kXcdBands, g = sb / (8u * kXcdBands);
+                    sub = p.sub_order[x * p.order_cap + g * kXcdBands + r];
                     return;
                 }
-#endif
                 sub = sb;
                 return;
             }
@@ -2034,7 +1936,7 @@ __device__ __forceinline__ void wave_body(const RenderParams& p, const Lds& L)
         if (state == LS_SETUP) {
             if (intersect_spheres<CNT, FEAT>(p, ray, hr, cnt) && mesh_needed<CNT, FEAT>(p, hr, ps.bounce)) {
                 trav_init<FEAT>(p, ray, hr.t, tr, L);
-                state = root_visit<CNT, FEAT>(p, ray, tr, L, cnt) ? LS_TRAV : LS_SHADE;
+                state = LS_TRAV;
             } else {
                 state = LS_SHADE;
             }
@@ -2145,7 +2047,7 @@ __device__ __forceinline__ void wave_body(const RenderParams& p, const Lds& L)
 }
 
 // ---- render service ---------------------------------------------------------
-// A session (vrhip_api.cpp) runs consecutive render launches on ONE
+// A session (vrhip_service.cpp) runs consecutive render launches on ONE
 // persistent kernel: the drain of launch L -- its last, longest paths, a
 // large share of a short launch (a 16-frame C3 shard of 3.7 M paths is
 // ~280 us of work next to a ~300-400 us longest path) --
@@ -2391,7 +2293,7 @@ __device__ __forceinline__ void service_body(const RenderParams& p, const Lds& L
         if (state == LS_SETUP) {
             if (intersect_spheres<false, FEAT>(p, ray, hr, cnt) && mesh_needed<false, FEAT>(p, hr, ps.bounce)) {
                 trav_init<FEAT>(p, ray, hr.t, tr, L);
-                state = root_visit<false, FEAT>(p, ray, tr, L, cnt) ? LS_TRAV : LS_SHADE;
+                state = LS_TRAV;
             } else {
                 state = LS_SHADE;
             }
@@ -2467,19 +2369,11 @@ __device__ __forceinline__ void service_body(const RenderParams& p, const Lds& L
     }
 }
 
-// residency of the service kernel (waves per SIMD; 0: the scene kernel's)
-#ifndef VR_SVC_WAVES
-#define VR_SVC_WAVES 0
-#endif
-constexpr int svc_waves(int stack, bool c) { return VR_SVC_WAVES > 0 && stack <= 24 ? VR_SVC_WAVES : path_waves(stack, c); }
-constexpr int svc_cache_nodes(int stack, int bt, bool c) {
-    return (163840 / (4 * svc_waves(stack, c) * 64 / bt) - bt - stack * bt * 4) / 56 > 0
-               ? (163840 / (4 * svc_waves(stack, c) * 64 / bt) - bt - stack * bt * 4) / 56 : 1;
-}
+// the service kernel runs at the scene kernel's residency and node cache (path_waves, path_cache_nodes)
 template <int STACK, uint32_t FEAT, int BT>
-__global__ void __launch_bounds__(BT, svc_waves(STACK, cornell_kernel<FEAT>())) render_service_kernel(const RenderParams p)
+__global__ void __launch_bounds__(BT, path_waves(STACK, cornell_kernel<FEAT>())) render_service_kernel(const RenderParams p)
 {
-    constexpr int CN = svc_cache_nodes(STACK, BT, cornell_kernel<FEAT>());
+    constexpr int CN = path_cache_nodes(STACK, BT, cornell_kernel<FEAT>());
     __shared__ int lds_stack[STACK * BT];
     __shared__ vr4 lds_nodes[3 * CN];
     __shared__ int2 lds_idx[CN];
@@ -2517,12 +2411,10 @@ constexpr uint32_t feature_class(uint32_t need) {
          : kClassHdriSphere;
 }
 
-// Multi-frame launches of fewer than 2^24 paths (shards) on the small-launch
-// kernels (F_SMALL: helper lanes, per-path costs, longest-first order) or,
-// with 0, on the whole-frame kernels in 256-thread blocks
-#ifndef VR_SHARD_SMALL
-#define VR_SHARD_SMALL 0
-#endif
+// Multi-frame launches of fewer than 2^24 paths (shards) run on the
+// whole-frame kernels in 256-thread blocks, not on the small-launch kernels
+// (F_SMALL: helper lanes, per-path costs, longest-first order), which only
+// one-frame launches take.
 template <int STACK, uint32_t FEAT>
 inline void launch_wave(const RenderParams& p, uint32_t n_tiles, hipStream_t s)
 {
@@ -2532,7 +2424,7 @@ inline void launch_wave(const RenderParams& p, uint32_t n_tiles, hipStream_t s)
         if (p.inline_prim) { launch_wave<STACK, FEAT | F_INLINE_PRIM>(p, n_tiles, s); return; }
     }
     if constexpr ((FEAT & (F_SMALL | F_COUNT_EXEC)) == 0u) {
-        if (p.small_blocks && (VR_SHARD_SMALL != 0 || (FEAT & F_INLINE_PRIM) != 0u)) {
+        if (p.small_blocks && (FEAT & F_INLINE_PRIM) != 0u) {
             launch_wave<STACK, FEAT | F_SMALL>(p, n_tiles, s);
             return;
         }
@@ -2545,7 +2437,7 @@ inline void launch_wave(const RenderParams& p, uint32_t n_tiles, hipStream_t s)
     constexpr int BT = ((FEAT & F_SMALL) != 0u) ? wave_block_small(STACK, C) : wave_block(STACK, C);
     constexpr int BTS = wave_block_small(STACK, C);
     // counted, or multi-frame shards on the whole-frame kernel: block size picked at run time below
-    constexpr bool runtime_bt = (FEAT & F_COUNT_EXEC) != 0u || ((FEAT & F_SMALL) == 0u && VR_SHARD_SMALL == 0);
+    constexpr bool runtime_bt = (FEAT & F_COUNT_EXEC) != 0u || (FEAT & F_SMALL) == 0u;
     constexpr int B = (runtime_bt && BTS != BT) ? 0 : BT;
     // blocks per CU: the kernel's full residency, or fewer under a waves-per-SIMD cap
     auto per_cu = [&](int bt) {
@@ -2588,7 +2480,7 @@ inline void launch_service_wave(const RenderParams& p, hipStream_t s)
     constexpr int BT = kBlockThreads;
     // the session's camera-ray hits (camera, scene and tiling are fixed for it)
     hipLaunchKernelGGL((primary_kernel<STACK, FEAT>), dim3(p.path_stride / kBlockThreads), dim3(kBlockThreads), 0, s, p);
-    const uint32_t per_cu = (uint32_t)(4 * svc_waves(STACK, C) * 64 / BT);
+    const uint32_t per_cu = (uint32_t)(4 * path_waves(STACK, C) * 64 / BT);
     if constexpr (sparse_ok<FEAT>()) {
         if (p.sparse_px) {                        // the listed pixels only
             hipLaunchKernelGGL((render_service_kernel<STACK, F | F_SPARSE, BT>), dim3(p.wave_blocks * per_cu), dim3(BT), 0, s, p);

@@ -1,4 +1,4 @@
-// vr_params.hpp -- launch parameters shared by the host API (vrhip_api.cpp)
+// vr_params.hpp -- launch parameters shared by the host API (vrhip_*.cpp)
 // and the gfx950 kernels (vr_kernel.hip).  Plain C++ types only.
 #pragma once
 #include <stddef.h>
@@ -56,7 +56,7 @@ enum Flags : uint32_t {
     F_SMALL = 1u << 14,
     // compile-time only: the render service's persistent kernel (render_service_kernel):
     // consecutive launches of a session from a descriptor ring, tagged
-    // primary records, results per launch slot (vrhip_api.cpp Session)
+    // primary records, results per launch slot (vr_ctx.hpp Session)
     F_SERVICE = 1u << 15,
     // compile-time only: the path kernel of HDRI mesh launches that skip the
     // pixels whose camera ray escapes (RenderParams::sparse_px): the primary
@@ -65,6 +65,8 @@ enum Flags : uint32_t {
     F_SPARSE = 1u << 16,
 };
 constexpr int kMaxFramesPerLaunch = 64;
+// device mesh layout: a leaf child index is ~((first_tri << kLeafCountBits) | count)
+constexpr int kLeafCountBits = 7;
 
 // counting variants, slots [0, kCounters): rays, node visits, vert0 slot
 // reads, triangle tests, attribute bytes, texture fetches, HDRI fetches, BRDF
@@ -102,6 +104,10 @@ static_assert((VR_QUEUES_LARGE & (VR_QUEUES_LARGE - 1)) == 0 && VR_QUEUES_LARGE 
 static_assert((VR_QUEUES_HDRI & (VR_QUEUES_HDRI - 1)) == 0 && VR_QUEUES_HDRI % 8 == 0,
               "VR_QUEUES_HDRI: power of two, multiple of 8");
 constexpr uint32_t kQueueStride = 256;
+// The sub-tiles (8x8 pixels) are dealt to the 8 XCDs in bands of this many,
+// so each XCD's L2 serves a coherent part of the image: the work queues, the
+// longest-first order lists (order_kernel) and the host's order buffers agree on it.
+constexpr uint32_t kXcdBands = 128;
 
 // ---- render service (vrhip_set_service; vr_kernel.hpp service_body) --------
 // A session is a run of render launches on one persistent kernel: the host
@@ -128,7 +134,7 @@ struct SvcHostCtl {                                // host-pinned (coherent)
     // kSvcClosed once it stops.  Retiring on its own (idle) it writes this
     // BEFORE its last look at `posted`, and the host reads it AFTER storing
     // `posted` (svc_post), so a launch posted as the kernel retires is seen
-    // as taken by exactly one side (svc_ring_wave, vrhip_api.cpp svc_post)
+    // as taken by exactly one side (svc_ring_wave, vrhip_service.cpp svc_post)
     uint32_t retired;
     uint32_t pad1[31];
     SvcLaunch desc[kSvcMaxLaunches];
