@@ -179,3 +179,139 @@ def render(scene: dict, frames: int = 1, times=None, first_frame: int = 1, libm:
     if rc != 0:
         raise RuntimeError(f"vro_render failed: {rc}")
     return accum, rgba, depth, (cnt.as_dict() if cnt is not None else None)
+
+
+# ---- the reference itself, compiled for the host (oracle/ref/README.md) ----------
+_REF_RECIPE = os.path.join(_HERE, "ref")
+_REF_OUT = os.path.join(_HERE, "_ref")            # build products; never committed
+_REF_CXX = os.environ.get("VRO_REF_CXX", os.path.join(os.environ.get("ROCM_PATH", "/opt/rocm"), "llvm", "bin", "clang++"))
+_REF_FLAGS = ["-O2", "-ffp-contract=off", "-fno-fast-math"]
+# the two sources with a construct a host compiler cannot parse: 5 asm statements, 1 launch
+_REF_KERNEL_FILES = ["cuda/src/PathTracer.cu", "cuda/include/PathTracer.cuh", "cuda/include/RayIntersection.cuh",
+                     "cuda/include/MathHelpers.cuh", "cuda/include/Utilities.cuh"]
+REF_VARIANTS = ["glibc_zero", "glibc_pattern", "portable_zero", "portable_pattern", "portable_ubsan"]
+
+
+def reference_path():
+    """The reference checkout: $VRO_REFERENCE, else ../reference beside this repository."""
+    p = os.environ.get("VRO_REFERENCE")
+    if not p:
+        p = os.path.join(os.path.dirname(os.path.dirname(_HERE)), "reference")
+    return p if os.path.isfile(os.path.join(p, "cuda", "src", "PathTracer.cu")) else None
+
+
+def ref_compiler_versions() -> dict:
+    first = lambda cmd: subprocess.run(cmd, capture_output=True, text=True).stdout.splitlines()[0].strip()
+    return {"clang++": first([_REF_CXX, "--version"]), "python": first(["python3", "--version"])}
+
+
+def build_reference(force: bool = False, variants=None):
+    """Compile the reference's kernel source and its SBVH builder for the host
+    into oracle/_ref/: ref_{glibc,portable}_{zero,pattern}, ref_portable_ubsan
+    (-fsanitize=float-cast-overflow, a stand-alone program), sbvh_driver and
+    rng_kat; with `variants`, only those kernel builds.  A target newer than
+    the recipe and the reference's sources is kept.  Returns {name: path}, or
+    None when no reference checkout exists or the recipe's compiler is missing."""
+    ref = reference_path()
+    if ref is None or not os.path.exists(_REF_CXX):
+        return None
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("vro_ref_rewrite", os.path.join(_REF_RECIPE, "rewrite.py"))
+    rewrite = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(rewrite)
+    names = ["ref_" + v for v in (variants or REF_VARIANTS)] + ([] if variants else ["sbvh_driver", "rng_kat"])
+    out = {n: os.path.join(_REF_OUT, n) for n in names}
+    recipe = [os.path.join(_REF_RECIPE, f) for f in sorted(os.listdir(_REF_RECIPE))]
+    recipe += [os.path.join(r, f) for r, _, fs in os.walk(os.path.join(_REF_RECIPE, "standin")) for f in fs]
+    recipe += [os.path.join(ref, f) for f in _REF_KERNEL_FILES + ["src/SBVH.cpp", "src/BVHNodes.cpp", "include/SBVH.h"]]
+    newest = max(os.path.getmtime(p) for p in recipe + [os.path.abspath(__file__), os.path.join(_HERE, "vro_math.c")])
+    stale = [n for n, p in out.items() if force or not os.path.exists(p) or os.path.getmtime(p) < newest]
+    if not stale:
+        return out
+    src = os.path.join(_REF_OUT, "src")
+    rewrite.rewrite_tree([os.path.join(ref, f) for f in _REF_KERNEL_FILES], src, want_asm=5, want_launch=1)
+    standin = os.path.join(_REF_RECIPE, "standin")
+    run = lambda cmd: subprocess.run(cmd, check=True, capture_output=True, text=True)
+    cc = _REF_CXX[:-2] if _REF_CXX.endswith("++") else _REF_CXX
+    math_o = os.path.join(_REF_OUT, "vro_math.o")
+    run([cc, "-std=gnu11", "-c"] + _REF_FLAGS + ["-I", _HERE, os.path.join(_HERE, "vro_math.c"), "-o", math_o])
+    for n in stale:
+        if not n.startswith("ref_"):
+            continue
+        libm, init = n[4:].split("_")
+        flags = list(_REF_FLAGS)
+        flags += ["-ftrivial-auto-var-init=" + ("pattern" if init == "pattern" else "zero")]
+        if init == "ubsan":
+            flags += ["-fsanitize=float-cast-overflow", "-g"]
+        if libm == "portable":
+            flags += ["-DVRO_REF_PORTABLE"]
+        run([_REF_CXX, "-std=c++14", "-w"] + flags + ["-I", standin, "-I", _HERE, "-I", src, "-x", "c++",
+             os.path.join(src, "PathTracer.cu"), os.path.join(_REF_RECIPE, "ref_driver.cpp"),
+             os.path.join(_REF_RECIPE, "standin_impl.cpp"), "-x", "none", math_o, "-lm", "-o", out[n]])
+    if "sbvh_driver" in stale:
+        run([_REF_CXX, "-std=c++14", "-w"] + _REF_FLAGS + ["-I", standin, "-I", os.path.join(ref, "include"),
+             os.path.join(ref, "src", "SBVH.cpp"), os.path.join(ref, "src", "BVHNodes.cpp"),
+             os.path.join(_REF_RECIPE, "sbvh_driver.cpp"), "-o", out["sbvh_driver"]])
+    if "rng_kat" in stale:
+        build_rng_kat(_REF_CXX)
+    return out
+
+
+def build_rng_kat(cxx: str = "g++") -> str:
+    """The known-answer program of the stand-in RNG (oracle/ref/rng_kat.cpp);
+    needs no reference checkout."""
+    os.makedirs(_REF_OUT, exist_ok=True)
+    exe = os.path.join(_REF_OUT, "rng_kat")
+    subprocess.run([cxx, "-std=c++14"] + _REF_FLAGS + ["-I", os.path.join(_REF_RECIPE, "standin"),
+                    os.path.join(_REF_RECIPE, "rng_kat.cpp"), "-o", exe], check=True, capture_output=True, text=True)
+    return exe
+
+
+def write_ref_blob(path: str, scene: dict, times) -> None:
+    """The scene file oracle/ref/ref_driver.cpp reads (layout: see its header)."""
+    u32 = lambda *v: np.array(v, dtype=np.uint32).tobytes()
+    f32 = lambda a: np.ascontiguousarray(a, dtype=np.float32).tobytes()
+    cam = scene["camera"]
+    with open(path, "wb") as f:
+        f.write(u32(0x31425256, scene["width"], scene["height"], len(times), bool(scene.get("cornell", False)),
+                    bool(scene.get("example_sphere", False)), bool(scene.get("view_brdf", False))))
+        for k in ("origin", "dir", "up", "right"):
+            f.write(f32(np.asarray(cam[k], dtype=np.float32)[:3]))
+        f.write(f32([cam["fov_scale"], scene.get("fresnel_coef", 0.1), scene.get("fresnel_pow", 3.0)]))
+        f.write(u32(*[int(t) & 0xFFFFFFFF for t in times]))
+        mesh = scene.get("mesh_flat")
+        if mesh is None:
+            f.write(u32(0, 0))
+        else:
+            f.write(u32(np.asarray(mesh["bvh"]).size // 4, np.asarray(mesh["verts"]).size // 4))
+            for k in ("bvh", "verts", "normals", "tangents", "uvs"):
+                f.write(f32(mesh[k]))
+        for key in ("hdr", "tex_diffuse", "tex_normal", "tex_specular"):
+            a = scene.get(key)
+            if a is None:
+                f.write(u32(0, 0))
+            else:
+                f.write(u32(a.shape[1], a.shape[0]))
+                f.write(f32(a))
+        brdf = scene.get("brdf")
+        f.write(u32(brdf is not None))
+        if brdf is not None:
+            f.write(f32(brdf))
+
+
+def render_reference(exe: str, scene: dict, times, workdir: str):
+    """Run one reference build on `scene`, frames 1..len(times).  Returns
+    (accum, rgba, depth, stderr text)."""
+    blob, out = os.path.join(workdir, "scene.blob"), os.path.join(workdir, "out.bin")
+    write_ref_blob(blob, scene, times)
+    r = subprocess.run([exe, blob, out], capture_output=True, text=True)
+    if r.returncode != 0:
+        raise RuntimeError(f"{os.path.basename(exe)} failed ({r.returncode}): {r.stderr[-2000:]}")
+    W, H = int(scene["width"]), int(scene["height"])
+    raw = open(out, "rb").read()
+    n = W * H
+    assert len(raw) == n * 24
+    accum = np.frombuffer(raw, np.float32, 4 * n, 0).reshape(H, W, 4).copy()
+    rgba = np.frombuffer(raw, np.uint8, 4 * n, 16 * n).reshape(H, W, 4).copy()
+    depth = np.frombuffer(raw, np.uint8, 4 * n, 20 * n).reshape(H, W, 4).copy()
+    return accum, rgba, depth, r.stderr

@@ -99,8 +99,46 @@ static BVHNode *buildTree(const vMeshData &_m, std::vector<unsigned int> &_ref, 
   return new InnerNode(box, l, r);
 }
 
+// A tree dumped by another builder (oracle/ref/sbvh_driver.cpp documents the
+// layout): nodes in preorder with their boxes, child links or leaf ranges,
+// then the triangle-reference array, loaded into the stand-in node classes.
+static bool loadTree(const char *_path, SBVH &_bvh)
+{
+  struct Node { uint32_t isLeaf; float lo[3], hi[3]; uint32_t a, b; };
+  FILE *f = std::fopen(_path, "rb");
+  if(!f)
+    return false;
+  uint32_t n[2];
+  bool ok = std::fread(n, 4, 2, f) == 2;
+  std::vector<Node> nodes(ok ? n[0] : 0);
+  _bvh.m_triIndices.resize(ok ? n[1] : 0);
+  ok = ok && std::fread(nodes.data(), sizeof(Node), nodes.size(), f) == nodes.size() &&
+       std::fread(_bvh.m_triIndices.data(), 4, n[1], f) == n[1];
+  std::fclose(f);
+  if(!ok || nodes.empty())
+    return false;
+  std::vector<BVHNode *> built(nodes.size(), nullptr);
+  for(size_t i = nodes.size(); i-- > 0;)       // preorder: children come after their parent
+  {
+    const Node &r = nodes[i];
+    ngl::Vec3 lo, hi;
+    lo.m_x = r.lo[0]; lo.m_y = r.lo[1]; lo.m_z = r.lo[2];
+    hi.m_x = r.hi[0]; hi.m_y = r.hi[1]; hi.m_z = r.hi[2];
+    if(r.isLeaf)
+      built[i] = new LeafNode(AABB(lo, hi), r.a, r.b);
+    else
+    {
+      if(r.a <= i || r.b <= i || r.a >= nodes.size() || r.b >= nodes.size())
+        return false;
+      built[i] = new InnerNode(AABB(lo, hi), built[r.a], built[r.b]);
+    }
+  }
+  _bvh.m_root.reset(built[0]);
+  return true;
+}
+
 // mesh file (tests/test_adapter.py): u32 nv, nt; f32 pos[3nv], nrm[3nv], tan[3nv], uv[2nv]; u32 tris[3nt]
-static bool loadMesh(const char *_path, vMeshData &_m)
+static bool loadMesh(const char *_path, vMeshData &_m, const char *_tree = nullptr)
 {
   FILE *f = std::fopen(_path, "rb");
   if(!f)
@@ -128,6 +166,8 @@ static bool loadMesh(const char *_path, vMeshData &_m)
   for(uint32_t t = 0; t < n[1]; ++t)
     for(int k = 0; k < 3; ++k)
       _m.m_triangles[t].m_indices[k] = tris[3 * t + k];
+  if(_tree)
+    return loadTree(_tree, _m.m_bvh);
   _m.m_bvh.m_triIndices.resize(n[1]);
   for(uint32_t t = 0; t < n[1]; ++t)
     _m.m_bvh.m_triIndices[t] = t;
@@ -286,6 +326,7 @@ static int runSceneFile(const char *_out, const char *_scene)
 //        adapter_driver <out> --scene <file>       a scene file (above) through every ingestion call
 //        adapter_driver <out> <mesh> [--flatten]   Cornell + the mesh (its SBVH flattened by the
 //                                                  adapter); --flatten: only write the flat arrays (no GPU)
+//        adapter_driver <out> <mesh> --flatten <tree>   the same, over a dumped tree instead of the driver's own
 //        adapter_driver <out> --devices <list>     write the device list init() parses from VRHIP_DEVICES (no GPU)
 int main(int argc, char **argv)
 {
@@ -306,7 +347,7 @@ int main(int argc, char **argv)
     return runSceneFile(argv[1], argv[3]);
   vMeshData mesh;
   const bool withMesh = argc >= 3;
-  if(withMesh && !loadMesh(argv[2], mesh))
+  if(withMesh && !loadMesh(argv[2], mesh, argc >= 5 && std::strcmp(argv[3], "--flatten") == 0 ? argv[4] : nullptr))
     return 3;
   if(argc >= 4 && std::strcmp(argv[3], "--flatten") == 0)
   {

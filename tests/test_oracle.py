@@ -1,8 +1,10 @@
-"""CPU tests of the oracle (oracle/vro.c) against every pin available.
+"""CPU tests of the oracle (oracle/vro.c) against its unit-level pins.
 
-The reference ships no tests, fixtures or golden vectors,
-and its CUDA kernel cannot be built here without stand-in headers (DESIGN.md
-"Oracle").  The oracle is pinned by:
+The reference ships no tests, fixtures or golden vectors.
+Whole images are pinned elsewhere: tests/test_reference_fixtures.py compares
+the oracle bit for bit with images the reference's own kernel source rendered
+when compiled for the host (oracle/ref/, DESIGN.md "Oracle").  Here the
+oracle's parts are pinned by:
   * RNG known answers produced by rocThrust itself (the third-party
     dependency the reference kernel uses), tests/golden/rng_kat.json;
   * the values SURVEY.md 8c recorded from its probe run of the reference
