@@ -931,12 +931,50 @@ __device__ __forceinline__ void probe_coherent(float& rand1, float& rand2)
 // bounce_step's exits call `sink` with the path's result (the render
 // service's store at each exit; the default stores nothing)
 struct NoSink { __device__ __forceinline__ void operator()(const vr4&) const {} };
-template <bool COUNT, uint32_t FEAT, bool DEPTH = true, typename Sink = NoSink>
+
+// The two exits that end a Cornell-box path without shading its hit: the
+// escape (:649-650) and, in the production kernels, the last bounce, of which
+// only the emission term is observable.  path_ends_short: the path waiting at
+// `hr` takes one of them; end_short: take it (the result in `out` and to
+// `sink`).  bounce_step takes them in place; the path pool's Cornell mesh
+// kernels (retire_first) take them ahead of the shading pass.
+__device__ __forceinline__ bool path_ends_short(const HitRec& hr, const PathState& ps)
+{
+    return !(hr.t < 1e20f) || ps.bounce == 3;
+}
+template <typename Sink>
+__device__ __forceinline__ void end_short(const HitRec& hr, PathState& ps, vr4& out, const Sink& sink)
+{
+    if (!(hr.t < 1e20f)) {
+        // Cornell escape (:649-650): radiance and .w are 0.  The x channel
+        // is -0.0 -- equal to +0 in every sum it enters (a running sum that
+        // starts at +0 under round-to-nearest is never -0, so adding -0 or +0
+        // leaves its bits unchanged) -- and marks the escape in the
+        // path-result scratch, which does not store .w (store_path).
+        out = mk4(-0.f, 0.f, 0.f, 0.f);
+        sink(out);
+        return;
+    }
+    // last bounce: only the emission term is observable; the material
+    // branch would only prepare a ray that is never traced
+    ps.accum = add4(ps.accum, mul4(ps.mask, emission_of(hr)));
+    ps.accum.w = ps.depth;
+    out = ps.accum;
+    sink(out);
+}
+
+// SHADE_ONLY (the kernels that retire ended paths first, retire_first): the
+// caller has taken the short exits, so the step never ends a path -- it
+// shades a hit below the last bounce and returns false, or finds a miss (a
+// fresh path whose camera ray escaped) and returns true with nothing done.
+template <bool COUNT, uint32_t FEAT, bool DEPTH = true, bool SHADE_ONLY = false, typename Sink = NoSink>
 __device__ __forceinline__ bool bounce_step(const RenderParams& p, Ray& ray, const HitRec& hr, PathState& ps,
                                             vr4& out, Cnt& cnt, const Sink& sink = Sink())
 {
     const bool hit = hr.t < 1e20f;
-    if (!hit) {
+    if constexpr (SHADE_ONLY) {
+        static_assert(!ref_alg<COUNT, FEAT>() && (FEAT & F_CORNELL) != 0u, "production Cornell kernels only");
+    } else if (!hit) {
         if (!HAS(F_CORNELL)) {                                    // :631-648
             float lx = atan2_p(ray.d.x, ray.d.z);
             float ly = acos_p(ray.d.y);
@@ -957,22 +995,11 @@ __device__ __forceinline__ bool bounce_step(const RenderParams& p, Ray& ray, con
             sink(out);
             return true;
         }
-        // Cornell escape (:649-650): radiance and .w are 0.  The x channel
-        // is -0.0 -- equal to +0 in every sum it enters (a running sum that
-        // starts at +0 under round-to-nearest is never -0, so adding -0 or +0
-        // leaves its bits unchanged) -- and marks the escape in the
-        // path-result scratch, which does not store .w (store_path).
-        out = mk4(-0.f, 0.f, 0.f, 0.f);
-        sink(out);
+        end_short(hr, ps, out, sink);                             // Cornell escape
         return true;
     }
-    if (!ref_alg<COUNT, FEAT>() && ps.bounce == 3) {
-        // last bounce: only the emission term is observable; the material
-        // branch below would only prepare a ray that is never traced
-        ps.accum = add4(ps.accum, mul4(ps.mask, emission_of(hr)));
-        ps.accum.w = ps.depth;
-        out = ps.accum;
-        sink(out);
+    if (!SHADE_ONLY && !ref_alg<COUNT, FEAT>() && ps.bounce == 3) {
+        end_short(hr, ps, out, sink);                             // last bounce
         return true;
     }
     // The diffuse branch's direction sample (the two draws after the Fresnel
@@ -1003,6 +1030,12 @@ __device__ __forceinline__ bool bounce_step(const RenderParams& p, Ray& ray, con
         sincos_p(rand1, &ssn, &scs);
     };
     if constexpr (SPEC && VR_SPEC_SAMPLE == 2) spec_sample();
+    // (after the sample, which needs no hit data: it covers the load of a
+    // fresh path's primary record.  An escaped camera ray costs its lane
+    // that sample and a slot in the passes until the next retirement -- a
+    // wasted slot of the kind the reorder removes, paid only by pixels
+    // whose camera ray leaves the box)
+    if constexpr (SHADE_ONLY) { if (!hit) return true; }
     Hit h;
     fill_hit<FEAT>(p, ray, hr, h);
     if constexpr (SPEC && VR_SPEC_SAMPLE == 1) spec_sample();
@@ -1118,7 +1151,7 @@ __device__ __forceinline__ bool bounce_step(const RenderParams& p, Ray& ray, con
     // around it on every bounce.  The untextured kernels keep it: they have
     // no spill there, and without it C2 lost 0.5 % (code placement) and C5's
     // one-frame kernel gained a spill.
-    constexpr bool LIVE4 = ref_alg<COUNT, FEAT>() || (FEAT & (F_TEX_DIFF | F_TEX_NORM | F_TEX_SPEC)) == 0u;
+    constexpr bool LIVE4 = !SHADE_ONLY && (ref_alg<COUNT, FEAT>() || (FEAT & (F_TEX_DIFF | F_TEX_NORM | F_TEX_SPEC)) == 0u);
     if (LIVE4 && ps.bounce == 4) {
         ps.accum.w = ps.depth;
         out = ps.accum;
@@ -1503,12 +1536,27 @@ __global__ void __launch_bounds__(kBlockThreads) primary_kernel(const RenderPara
 // Every path runs exactly the operations of trace(); only the interleaving
 // of paths on the SIMD changes, so results are bit-identical.
 // finish_kernel then sums each pixel's paths in path order.
+//
+// When the traversal loop leaves for the shading pass (shade_now): in steady
+// state every lane either traverses or waits for shading, n_trav + n_shade =
+// 64, so the ratio test n_shade * VR_SHADE_RATIO >= n_trav * VR_SHADE_RATIO_DEN
+// sets the size of the pass -- 32 waiting lanes at 1 : 1 -- and VR_SHADE_BATCH
+// (16) never binds before it; it only matters while lanes are idle (the
+// drain).  The earlier sweeps of the batch (8 .. 32, all "within noise")
+// therefore changed nothing; the ratio's sweep is in DESIGN.md 8.
 #ifndef VR_SHADE_BATCH
 #define VR_SHADE_BATCH 16
 #endif
 #ifndef VR_SHADE_RATIO
 #define VR_SHADE_RATIO 1
 #endif
+#ifndef VR_SHADE_RATIO_DEN
+#define VR_SHADE_RATIO_DEN 1
+#endif
+__device__ __forceinline__ bool shade_now(int n_shade, int n_trav)
+{
+    return n_shade >= VR_SHADE_BATCH && n_shade * VR_SHADE_RATIO >= n_trav * VR_SHADE_RATIO_DEN;
+}
 // Once the queues are drained, the paths waiting to be shaded are shaded
 // together once n_shade * VR_DRAIN_SHADE_NUM >= n_trav * VR_DRAIN_SHADE_DEN
 // (or no lane traverses): each shading round costs the wave a whole pass
@@ -1523,6 +1571,25 @@ __global__ void __launch_bounds__(kBlockThreads) primary_kernel(const RenderPara
 #ifndef VR_DRAIN_SHADE_DEN
 #define VR_DRAIN_SHADE_DEN 1
 #endif
+// Retire first (the Cornell-box mesh kernels that start from primary records:
+// C2's service, whole-frame and shard kernels, the Cornell mesh class).  A
+// path waits for shading four times, and the fourth time -- or after an
+// escape -- it only takes one of bounce_step's short exits (end_short).
+// These kernels take the short exits and refill the lanes before the shading
+// pass, when the traversal loop exits: the pass holds only lanes with a hit
+// to shade, and a refilled lane's new path is shaded in the same pass instead
+// of the next one; the shading step then never ends a path and no refill
+// follows it.  (Retiring inside the traversal loop as soon as 8 / 16 / 32
+// lanes could, so that the new paths' primary records load under the
+// following trav_iters, measured slower -- 8: -2.7 %, 16 / 32: -0.5 % --
+// with more passes through start() for fewer lanes each)  The HDRI kernels' shading step can itself
+// end a path (the miss fetches the map), and the one-frame kernels start at
+// the camera ray: both keep shade-then-refill.
+template <uint32_t FEAT>
+constexpr bool retire_first() {
+    return (FEAT & (F_EXACT | F_CLASS)) != 0u && (FEAT & F_CORNELL) != 0u && (FEAT & F_MESH) != 0u &&
+           (FEAT & (F_INLINE_PRIM | F_SMALL)) == 0u;
+}
 enum LaneState : int { LS_SETUP = 0, LS_TRAV = 1, LS_SHADE = 2, LS_DONE = 3, LS_CAMERA = 4, LS_HELP = 5, LS_HELPDONE = 6 };
 
 // Helpers (the launch's drain).  Once the work queues are empty, a wave's
@@ -1914,6 +1981,25 @@ __device__ __forceinline__ void wave_body(const RenderParams& p, const Lds& L)
         state = LS_SHADE;
     };
     start(cur_sub, cur_q, (uint32_t)lane);
+    // refill: lanes whose path ended take the next items (one start() site
+    // in the loop)
+    auto refill = [&](bool ended) {
+        const unsigned long long em = __ballot(ended);
+        if (em != 0ull) {
+            const uint32_t need = (uint32_t)__popcll(em);
+            uint32_t nsub = cur_sub, nq = cur_q;
+            if (next + need > 64u && cur_sub != ~0u) grab(nsub, nq);
+            if (ended) {
+                const uint32_t r = next + __builtin_amdgcn_mbcnt_hi((uint32_t)(em >> 32),
+                                                                    __builtin_amdgcn_mbcnt_lo((uint32_t)em, 0u));
+                if (r < 64u) start(cur_sub, cur_q, r);
+                else start(nsub, nq, r - 64u);
+            }
+            if (next + need > 64u) { cur_sub = nsub; cur_q = nq; next = next + need - 64u; }
+            else next += need;
+        }
+    };
+    constexpr bool RETIRE = retire_first<FEAT>();
 
     for (;;) {
         if constexpr (age_prio<FEAT>()) {
@@ -1944,12 +2030,30 @@ __device__ __forceinline__ void wave_body(const RenderParams& p, const Lds& L)
         if (HAS(F_MESH)) {
             for (;;) {
                 const int n_trav = __popcll(__ballot(state == LS_TRAV || state == LS_HELP));
-                if (n_trav == 0) break;
-                const int n_shade = __popcll(__ballot(state == LS_SHADE));
-                if (n_shade >= VR_SHADE_BATCH && n_shade * VR_SHADE_RATIO >= n_trav) break;
-                // queue drained: no lane will be refilled; shade in batches
-                if (cur_sub == ~0u && n_shade > 0 && n_shade * VR_DRAIN_SHADE_NUM >= n_trav * VR_DRAIN_SHADE_DEN)
-                    break;
+                if constexpr (RETIRE) {
+                    // retire_first: the shading pass is next (the conditions
+                    // of the other kernels, below); the ended paths leave first
+                    const int n_shade = __popcll(__ballot(state == LS_SHADE));
+                    const bool leave = n_trav == 0 || shade_now(n_shade, n_trav) ||
+                                       (cur_sub == ~0u && n_shade > 0 &&
+                                        n_shade * VR_DRAIN_SHADE_NUM >= n_trav * VR_DRAIN_SHADE_DEN);
+                    if (leave) {
+                        const bool rt = state == LS_SHADE && path_ends_short(hr, ps);
+                        if (rt) {
+                            vr4 out;
+                            end_short(hr, ps, out, [&](const vr4& o) { store_path_rgb(p, lane_q(), lane_slot(), o); });
+                        }
+                        refill(rt);
+                        break;
+                    }
+                } else {
+                    if (n_trav == 0) break;
+                    const int n_shade = __popcll(__ballot(state == LS_SHADE));
+                    if (shade_now(n_shade, n_trav)) break;
+                    // queue drained: no lane will be refilled; shade in batches
+                    if (cur_sub == ~0u && n_shade > 0 && n_shade * VR_DRAIN_SHADE_NUM >= n_trav * VR_DRAIN_SHADE_DEN)
+                        break;
+                }
                 if constexpr (helpers<FEAT>()) {
                     if (cur_sub == ~0u || __ballot(state == LS_HELP || state == LS_HELPDONE) != 0ull)
                         (void)help_step(p, lane, state, pend, slot, ray, tr, L);
@@ -2000,7 +2104,11 @@ __device__ __forceinline__ void wave_body(const RenderParams& p, const Lds& L)
                  (FEAT & (F_CORNELL | F_TEX_DIFF | F_TEX_NORM | F_TEX_SPEC)) == 0u) ||
                 ((VR_WAVE_AT_EXIT & 2) && CORN && !INL && (FEAT & F_SMALL) == 0u) ||
                 ((VR_WAVE_AT_EXIT & 4) && CORN && INL);
-            if constexpr (AT_EXIT) {
+            if constexpr (RETIRE) {
+                // the short exits are taken: a hit is shaded, a fresh path
+                // whose camera ray escaped waits for the next retirement
+                if (!bounce_step<CNT, FEAT, false, true>(p, ray, hr, ps, out, cnt)) state = LS_SETUP;
+            } else if constexpr (AT_EXIT) {
                 if (bounce_step<CNT, FEAT, INL && !EARLY_DEPTH>(p, ray, hr, ps, out, cnt, [&](const vr4& o) {
                         if constexpr (INL && !EARLY_DEPTH) store_path(p, lane_q(), lane_slot(), o, ps.depth);
                         else store_path_rgb(p, lane_q(), lane_slot(), o);
@@ -2027,20 +2135,7 @@ __device__ __forceinline__ void wave_body(const RenderParams& p, const Lds& L)
                 state = LS_SETUP;
             }
         }
-        const unsigned long long em = __ballot(ended);
-        if (em != 0ull) {
-            const uint32_t need = (uint32_t)__popcll(em);
-            uint32_t nsub = cur_sub, nq = cur_q;
-            if (next + need > 64u && cur_sub != ~0u) grab(nsub, nq);
-            if (ended) {
-                const uint32_t r = next + __builtin_amdgcn_mbcnt_hi((uint32_t)(em >> 32),
-                                                                    __builtin_amdgcn_mbcnt_lo((uint32_t)em, 0u));
-                if (r < 64u) start(cur_sub, cur_q, r);
-                else start(nsub, nq, r - 64u);
-            }
-            if (next + need > 64u) { cur_sub = nsub; cur_q = nq; next = next + need - 64u; }
-            else next += need;
-        }
+        if constexpr (!RETIRE) refill(ended);
         if (__ballot(state != LS_DONE) == 0ull) break;
     }
     if (CNT) flush_counts(p, cnt, lane, true);
@@ -2288,59 +2383,11 @@ __device__ __forceinline__ void service_body(const RenderParams& p, const Lds& L
             __builtin_amdgcn_s_sleep(32);
         }
     };
-    // every lane idle (LS_DONE): the loop's refill waits for the first chunk
-    for (;;) {
-        if (state == LS_SETUP) {
-            if (intersect_spheres<false, FEAT>(p, ray, hr, cnt) && mesh_needed<false, FEAT>(p, hr, ps.bounce)) {
-                trav_init<FEAT>(p, ray, hr.t, tr, L);
-                state = LS_TRAV;
-            } else {
-                state = LS_SHADE;
-            }
-        }
-        if (HAS(F_MESH)) {
-            for (;;) {
-                const int n_trav = __popcll(__ballot(state == LS_TRAV));
-                if (n_trav == 0) break;
-                const int n_shade = __popcll(__ballot(state == LS_SHADE));
-                if (n_shade >= VR_SHADE_BATCH && n_shade * VR_SHADE_RATIO >= n_trav) break;
-                if (cur_sub == ~0u && n_shade > 0 && n_shade * VR_DRAIN_SHADE_NUM >= n_trav * VR_DRAIN_SHADE_DEN) break;
-                if (state == LS_TRAV) {
-                    trav_iter<STACK, false, FEAT>(p, ray, tr, L, cnt);
-                    if (any_hit_enough<false, FEAT>(p, ps.bounce) && tr.best >= 0) tr.nodeAddr = kSentinel;
-                    if (tr.nodeAddr == kSentinel) {
-                        trav_finish(tr, hr);
-                        state = LS_SHADE;
-                    }
-                }
-            }
-        }
-        bool ended = false;
-        if (state == LS_SHADE) {
-            vr4 out;
-            // Cornell-box and textured kernels store the result at each of
-            // bounce_step's exits: stored after the join, the merged radiance
-            // was spilled around it -- three scratch loads on every bounce of
-            // C2's service kernel (6 spills -> 0, C2 +0.5 %, C3 +1 %); the
-            // plain HDRI kernels (C5, no spills) keep the join (-0.4 % without)
-            constexpr bool AT_EXIT = (FEAT & (F_CORNELL | F_TEX_DIFF | F_TEX_NORM | F_TEX_SPEC)) != 0u;
-            bool done;
-            if constexpr (AT_EXIT) {
-                done = bounce_step<false, FEAT, false>(p, ray, hr, ps, out, cnt, [&](const vr4& o) {
-                    svc_store_path(p, q >> 8, q & 0xffu, slot, o);
-                });
-            } else {
-                done = bounce_step<false, FEAT, false>(p, ray, hr, ps, out, cnt);
-                if (done) svc_store_path(p, q >> 8, q & 0xffu, slot, out);
-            }
-            if (done) ended = true;
-            else state = LS_SETUP;
-        }
-        // refill: lanes whose path ended take the next items; when every
-        // lane is idle the wave waits for the ring's next chunk and all 64
-        // lanes take it (one start() site, so one inlined copy of it)
-        bool take = ended;
-        bool over = false;
+    // refill: lanes whose path ended (`take`) take the next items; when every
+    // lane is idle the wave waits for the ring's next chunk and all 64
+    // lanes take it (one start() site, so one inlined copy of it).  False:
+    // the session is over for this wave.
+    auto refill = [&](bool take) -> bool {
         for (;;) {
             const unsigned long long em = __ballot(take);
             if (em != 0ull) {
@@ -2360,12 +2407,94 @@ __device__ __forceinline__ void service_body(const RenderParams& p, const Lds& L
                 if (next + need > 64u) { cur_sub = nsub; cur_q = nq; cur_L = nL; cslot ^= 1u; next = next + need - 64u; }
                 else next += need;
             }
-            if (__ballot(state != LS_DONE) != 0ull) break;
-            if (ring == DONE || !wait_chunk()) { over = true; break; }
+            if (__ballot(state != LS_DONE) != 0ull) return true;
+            if (ring == DONE || !wait_chunk()) return false;
             next = 0u;
             take = true;
         }
+    };
+    constexpr bool RETIRE = retire_first<FEAT>();
+    // every lane idle (LS_DONE): the loop's refill waits for the first chunk
+    for (;;) {
+        if (state == LS_SETUP) {
+            if (intersect_spheres<false, FEAT>(p, ray, hr, cnt) && mesh_needed<false, FEAT>(p, hr, ps.bounce)) {
+                trav_init<FEAT>(p, ray, hr.t, tr, L);
+                state = LS_TRAV;
+            } else {
+                state = LS_SHADE;
+            }
+        }
+        bool over = false;
+        if (HAS(F_MESH)) {
+            for (;;) {
+                const int n_trav = __popcll(__ballot(state == LS_TRAV));
+                if constexpr (RETIRE) {
+                    // retire_first: the shading pass is next (the conditions
+                    // of the other kernels, below); the ended paths leave
+                    // first, and a wave with every lane idle waits in refill.
+                    // (The conditions are written out per form, here and in
+                    // wave_body: computed once ahead of the branch, the C2
+                    // service kernel spilled 14 VGPRs and the Cornell mesh
+                    // class 3.)
+                    const int n_shade = __popcll(__ballot(state == LS_SHADE));
+                    const bool leave = n_trav == 0 || shade_now(n_shade, n_trav) ||
+                                       (cur_sub == ~0u && n_shade > 0 &&
+                                        n_shade * VR_DRAIN_SHADE_NUM >= n_trav * VR_DRAIN_SHADE_DEN);
+                    if (leave) {
+                        const bool rt = state == LS_SHADE && path_ends_short(hr, ps);
+                        if (rt) {
+                            vr4 out;
+                            end_short(hr, ps, out, [&](const vr4& o) { svc_store_path(p, q >> 8, q & 0xffu, slot, o); });
+                        }
+                        over = !refill(rt);
+                        break;
+                    }
+                } else {
+                    if (n_trav == 0) break;
+                    const int n_shade = __popcll(__ballot(state == LS_SHADE));
+                    if (shade_now(n_shade, n_trav)) break;
+                    if (cur_sub == ~0u && n_shade > 0 && n_shade * VR_DRAIN_SHADE_NUM >= n_trav * VR_DRAIN_SHADE_DEN) break;
+                }
+                if (state == LS_TRAV) {
+                    trav_iter<STACK, false, FEAT>(p, ray, tr, L, cnt);
+                    if (any_hit_enough<false, FEAT>(p, ps.bounce) && tr.best >= 0) tr.nodeAddr = kSentinel;
+                    if (tr.nodeAddr == kSentinel) {
+                        trav_finish(tr, hr);
+                        state = LS_SHADE;
+                    }
+                }
+            }
+        }
         if (over) break;
+        bool ended = false;
+        if (state == LS_SHADE) {
+            vr4 out;
+            // Cornell-box and textured kernels store the result at each of
+            // bounce_step's exits: stored after the join, the merged radiance
+            // was spilled around it -- three scratch loads on every bounce of
+            // C2's service kernel (6 spills -> 0, C2 +0.5 %, C3 +1 %); the
+            // plain HDRI kernels (C5, no spills) keep the join (-0.4 % without)
+            constexpr bool AT_EXIT = (FEAT & (F_CORNELL | F_TEX_DIFF | F_TEX_NORM | F_TEX_SPEC)) != 0u;
+            bool done;
+            if constexpr (RETIRE) {
+                // the short exits are taken: a hit is shaded, a fresh path
+                // whose camera ray escaped waits for the next retirement
+                done = bounce_step<false, FEAT, false, true>(p, ray, hr, ps, out, cnt);
+            } else if constexpr (AT_EXIT) {
+                done = bounce_step<false, FEAT, false>(p, ray, hr, ps, out, cnt, [&](const vr4& o) {
+                    svc_store_path(p, q >> 8, q & 0xffu, slot, o);
+                });
+                ended = done;
+            } else {
+                done = bounce_step<false, FEAT, false>(p, ray, hr, ps, out, cnt);
+                if (done) svc_store_path(p, q >> 8, q & 0xffu, slot, out);
+                ended = done;
+            }
+            if (!done) state = LS_SETUP;
+        }
+        if constexpr (!RETIRE) {
+            if (!refill(ended)) break;
+        }
     }
 }
 
