@@ -4,8 +4,12 @@ Run by hand where a reference checkout exists (oracle/ref/README.md):
 
     python tests/golden/gen_ref_golden.py [--check] [case ...]
 
+    python tests/golden/gen_ref_golden.py --flags [--check]
+
 With --check nothing is written: the fresh arrays are compared with the
-committed files, key by key.
+committed files, key by key.  --flags renders the 256 scene-flag combinations
+of tests/flag_lattice.py instead of the cases and writes ref_flags.npz, which
+holds digests, not images (oracle/ref/README.md has the layout).
 
 Every case of tests/ref_cases.py is rendered by the `zero`-initialised
 reference in both libm modes, by the `pattern`-initialised one (pixels that
@@ -19,9 +23,11 @@ import hashlib
 import json
 import os
 import re
+import shutil
 import subprocess
 import sys
 import tempfile
+import threading
 
 import numpy as np
 
@@ -170,6 +176,119 @@ def generate(names, check=False):
     print("pixels differing from the oracle, all cases:", total_diff)
 
 
+MIN_FLAG_PAIRS = 16          # of the 128 single-flag pairs of each flag, how many must differ
+_ORACLE_LOCK = threading.Lock()   # the reference runs are processes; the oracle renders one scene at a time
+
+
+def flags_point(builds, combo, workdir):
+    """One lattice point through the five reference builds and both oracle modes."""
+    import flag_lattice as fl
+    name = fl.name_of(combo)
+    sc = fl.scene_of(combo)
+    times = fl.TIMES
+    os.makedirs(workdir, exist_ok=True)
+    pa, pr, pd, _ = po.render_reference(builds["ref_portable_zero"], sc, times, workdir)
+    ga, gr, _, _ = po.render_reference(builds["ref_glibc_zero"], sc, times, workdir)
+    undefined = np.zeros(pa.shape[:2], bool)
+    for libm, (za, zr, zd) in (("portable", (pa, pr, pd)), ("glibc", (ga, gr, None))):
+        qa, qr, qd, _ = po.render_reference(builds[f"ref_{libm}_pattern"], sc, times, workdir)
+        undefined |= (qa.view(np.uint32) != za.view(np.uint32)).any(-1) | (qr != zr).any(-1)
+        if zd is not None:
+            undefined |= (qd != zd).any(-1)
+    ua, ur, ud, err = po.render_reference(builds["ref_portable_ubsan"], sc, times, workdir)
+    assert np.array_equal(ua.view(np.uint32), pa.view(np.uint32)) and np.array_equal(ud, pd), name
+    locs, other = ubsan_locations(err, None)
+    assert not other, f"{name}: UBSan reports outside the depth byte: {other}"
+    with _ORACLE_LOCK:
+        oa, orgba, od, _ = po.render(sc, frames=len(times), times=times, libm=po.LIBM_PORTABLE)
+        oga, ogr, _, _ = po.render(sc, frames=len(times), times=times, libm=po.LIBM_GLIBC)
+    diff = ((oa.view(np.uint32) != pa.view(np.uint32)).any(-1) | (orgba != pr).any(-1) |
+            (oga.view(np.uint32) != ga.view(np.uint32)).any(-1) | (ogr != gr).any(-1) |
+            ((od != pd).any(-1) & (od[..., 0] != 0)))
+    assert np.any(pa[..., :3] != 0) and np.any(pr[..., :3] != 0), f"{name}: a black image"
+    return dict(accum_portable=sha(pa), rgba_portable=sha(pr), depth_portable=sha(fl.masked_depth(pd, od)),
+                accum_glibc=sha(ga), rgba_glibc=sha(gr), undefined=undefined, ubsan=locs,
+                inputs=sha(json.dumps(rc.input_digests(sc), sort_keys=True).encode()),
+                oracle=sha(oa), oracle_rgba=sha(orgba), differ=int(diff.sum()))
+
+
+def generate_flags(check=False):
+    """tests/golden/ref_flags.npz: per combination of tests/flag_lattice.py, digests
+    of what the reference renders (256 float images do not fit the size cap)."""
+    from concurrent.futures import ThreadPoolExecutor
+    import flag_lattice as fl
+    builds = po.build_reference()
+    if builds is None:
+        raise SystemExit("no reference checkout (set VRO_REFERENCE)")
+    po.build()
+    po.lib()
+    combos = fl.combos()
+    fl.scene_of(combos[-1])                          # the shared inputs, made once before the threads start
+    with tempfile.TemporaryDirectory() as d:
+        with ThreadPoolExecutor(max_workers=min(8, os.cpu_count() or 1)) as pool:
+            pts = list(pool.map(lambda ic: flags_point(builds, ic[1], os.path.join(d, str(ic[0]))), enumerate(combos)))
+    n_px = fl.W * fl.H
+    counts = np.array([int(p["undefined"].sum()) for p in pts], np.int32)
+    for combo, n in zip(combos, counts):
+        c = dict(zip(fl.FLAGS, combo))
+        may = not c["cornell"] and c["example"] and (c["tex_d"] or c["tex_n"] or c["tex_s"])
+        assert n <= MAX_UNDEFINED * n_px, (fl.name_of(combo), int(n))
+        assert may or n == 0, f"{fl.name_of(combo)}: {n} undefined pixels outside HDRI + example sphere + a map"
+    index = {c: i for i, c in enumerate(combos)}
+    pairs = {}                                       # per flag: (accumulations that differ, RGBA8 images that differ)
+    for k, flag in enumerate(fl.FLAGS):
+        off = [c for c in combos if not c[k]]
+        pairs[flag] = tuple(sum(pts[index[c]][what] != pts[index[c[:k] + (1,) + c[k + 1:]]][what] for c in off)
+                            for what in ("oracle", "oracle_rgba"))
+        assert len(off) == 128 and min(pairs[flag]) >= MIN_FLAG_PAIRS, (flag, pairs[flag])
+    masks, mask_index = [], []
+    for p in pts:
+        packed = np.packbits(p["undefined"].reshape(-1))
+        for i, m in enumerate(masks):
+            if np.array_equal(m, packed):
+                break
+        else:
+            i = len(masks)
+            masks.append(packed)
+        mask_index.append(i)
+    sc_all = fl.scene_of(combos[-1])
+    arrays = {k: v for k, v in rc.input_digests(sc_all).items() if k != "scalars"}
+    meta = dict(flags=list(fl.FLAGS), width=fl.W, height=fl.H, frames=len(fl.TIMES), times=fl.TIMES, inputs=arrays,
+                ubsan=sorted({loc for p in pts for loc in p["ubsan"]}), compilers=po.ref_compiler_versions())
+    out = {f"{k}_sha256": np.array([p[k] for p in pts]) for k in
+           ("accum_portable", "rgba_portable", "depth_portable", "accum_glibc", "rgba_glibc", "inputs")}
+    out["undefined_count"] = counts
+    out["undefined_index"] = np.array(mask_index, np.int16)
+    out["undefined_masks"] = np.stack(masks)
+    out["meta"] = np.array(json.dumps(meta, sort_keys=True))
+    print(f"combinations {len(combos)}  distinct images {len({p['oracle'] for p in pts})} "
+          f"(RGBA8 {len({p['oracle_rgba'] for p in pts})})  "
+          f"undefined: max {int(counts.max())} of {n_px}, in {int((counts > 0).sum())} combinations, "
+          f"{len(masks)} distinct masks  ubsan {meta['ubsan']}")
+    print("single-flag pairs that differ, of 128 (accum, RGBA8):", pairs)
+    print("pixels differing from the oracle, all combinations:", sum(p["differ"] for p in pts))
+    path = os.path.join(HERE, "ref_flags.npz")
+    if check:
+        old = np.load(path)
+        assert sorted(old.files) == sorted(out), f"{path}: keys differ"
+        bad = [k for k in out if np.asarray(out[k]).tobytes() != old[k].tobytes() or np.asarray(out[k]).dtype != old[k].dtype]
+        assert not bad, f"{path}: a fresh run differs in {bad}"
+        size = os.path.getsize(path)
+        assert size <= MAX_FILE, f"{path} is larger than golden_images.npz ({MAX_FILE})"
+        print(f"  -> {os.path.relpath(path, REPO)} reproduced ({len(out)} arrays, {size} bytes)")
+        return
+    with tempfile.TemporaryDirectory() as d:
+        fresh = os.path.join(d, "ref_flags.npz")
+        np.savez_compressed(fresh, **out)
+        size = os.path.getsize(fresh)
+        assert size <= MAX_FILE, f"ref_flags.npz would be larger than golden_images.npz ({size} > {MAX_FILE})"
+        shutil.move(fresh, path)
+    print(f"  -> {os.path.relpath(path, REPO)}  {size} bytes")
+
+
 if __name__ == "__main__":
-    args = [a for a in sys.argv[1:] if a != "--check"]
-    generate(args or list(rc.CASES), check="--check" in sys.argv[1:])
+    args = [a for a in sys.argv[1:] if a not in ("--check", "--flags")]
+    if "--flags" in sys.argv[1:]:
+        generate_flags(check="--check" in sys.argv[1:])
+    else:
+        generate(args or list(rc.CASES), check="--check" in sys.argv[1:])

@@ -1,10 +1,12 @@
-"""GPU parity of the feature-class kernels (vr_cls_*.hip): every flag
-combination the Qt UI produces outside the five exact BASELINE feature sets
+"""GPU parity of the feature-class kernels (vr_cls_*.hip), which take the flag
+combinations the Qt UI produces outside the five exact BASELINE feature sets
 (vr_kernel.hpp feature_class) -- texture maps and the BRDF view tested at run
-time, Cornell / HDRI and mesh / spheres fixed at compile time -- bit-exact
-against the portable-libm oracle (oracle/vro.c, the line-cited restatement of
-PathTracer.cu:597-770), on multi-frame, one-frame (inline camera ray), tiled
-(shard) and render-service launches.
+time, Cornell / HDRI and mesh / spheres fixed at compile time: nine of those
+combinations at working sizes, bit-exact against the portable-libm oracle
+(oracle/vro.c, the line-cited restatement of PathTracer.cu:597-770), on
+multi-frame, one-frame (inline camera ray), tiled (shard) and render-service
+launches.  Every flag combination, at 32x32, is swept by
+tests/test_flag_lattice.py.
 """
 import numpy as np
 import pytest
