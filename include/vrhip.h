@@ -144,6 +144,38 @@ int vrhip_upload_mesh_indexed(vrhip_ctx *ctx, const float *positions, const floa
 int vrhip_upload_mesh_device(vrhip_ctx *ctx, const float *d_positions, const float *d_normals,
                              const float *d_tangents, const float *d_uvs, uint32_t n_verts,
                              const uint32_t *d_tris, uint32_t n_tris, uint32_t max_leaf_tris);
+/* vrhip_upload_mesh_device with a choice of tree; everything said above holds
+ * for both (arguments, checks and their order, transactional behaviour, the
+ * refusal on a vrhip_create_multi context, "returns when the build has
+ * finished"); an unknown builder is VRHIP_ERR_INVALID.
+ *   VRHIP_DEVBVH_MORTON  the tree described above: exactly
+ *     vrhip_upload_mesh_device, which forwards here.  Cheapest to build.
+ *   VRHIP_DEVBVH_SAH  the tree vrhip_build_flat / vrhip_upload_mesh_indexed
+ *     build on the host, built on the device: binned SAH with object splits,
+ *     128 bins per axis over the centroid bounds, SAH costs 1 for a node and a
+ *     triangle, the split after the first strictly cheapest bin (axes x, y, z
+ *     in order), a leaf where max_leaf_tris allows one and splitting does not
+ *     pay, coincident centroids halved by order, depth at most 30; a single
+ *     triangle is stored twice under two leaves.  Every decision is taken from
+ *     min/max boxes, counts and fp64 arithmetic, and the partition is stable,
+ *     so vrhip_export_mesh_flat returns the node array of vrhip_build_flat
+ *     byte for byte, with each leaf's triangles in ascending input index (the
+ *     host's order inside a leaf may differ; boxes holding both -0 and +0 at an
+ *     extreme may differ in that zero's sign).  vrhip_bvh_info reports the
+ *     tree's real depth.  A leaf that would hold 128 or more triangles (only
+ *     at the depth cap) is VRHIP_ERR_BVH, as it is for such a tree uploaded
+ *     flat.  The host builder's experiment switches VRHIP_SAH_NODE_COST and
+ *     VRHIP_SBVH_ALPHA are ignored.  Costs one small read-back per tree level.
+ * Added without an ABI version change (ABI 6 gained this symbol and
+ * vrhip_device_sah_scratch_bytes and changed no other). */
+typedef enum vrhip_device_builder { VRHIP_DEVBVH_MORTON = 0, VRHIP_DEVBVH_SAH = 1 } vrhip_device_builder;
+int vrhip_upload_mesh_device_ex(vrhip_ctx *ctx, const float *d_positions, const float *d_normals,
+                                const float *d_tangents, const float *d_uvs, uint32_t n_verts,
+                                const uint32_t *d_tris, uint32_t n_tris, uint32_t max_leaf_tris,
+                                uint32_t builder);
+/* Bytes of device scratch a VRHIP_DEVBVH_SAH build of n_tris triangles takes
+ * while it runs (freed before the call returns); 0 without a device. */
+size_t vrhip_device_sah_scratch_bytes(uint32_t n_tris);
 /* The resident mesh, whichever upload call brought it, rewritten on the host
  * in the reference layout vrhip_upload_mesh_flat takes (what the oracle, or a
  * caller caching a tree, needs of a device-built tree).  Nodes are numbered

@@ -1,19 +1,25 @@
 #!/usr/bin/env python3
 """Cost of getting a mesh into the renderer: the BVH built on the device from
-device-resident triangles (initMeshDevice) against the host path (build_flat,
-then initMesh), and what the device's simpler tree costs at render time.
+device-resident triangles (initMeshDevice, its Morton and its SAH builder)
+against the host path (build_flat, then initMesh), and what each tree costs at
+render time.
 
   python scripts/build_cost.py [--out build_cost.json] [--frames 16] [--steps 4]
 
 One JSON line per mesh (the 10k-triangle knot in scene C2, the 1M-triangle knot
 in scene C5):
-  device_build_ms   median of 5 builds into fresh contexts after one warm-up,
-                    wall clock around the synchronous call
+  device_build_ms, sah_build_ms   median of 5 builds into fresh contexts after
+                    one warm-up, wall clock around the synchronous call (the
+                    Morton and the SAH builder)
+  sah_build_vs_host   sah_build_ms over the host path (build_flat + initMesh)
+  sah_arena_bytes, sah_arena_bytes_per_tri   the SAH build's device scratch
   host_build_flat_ms, host_init_mesh_ms   the host path in the same process
-  depth_device, depth_host                as vrhip_bvh_info reports them
-  mpaths_device_tree, mpaths_host_tree    frames-per-step render rate of the
-                    scene on each tree, measured as scripts/ab.py does (median
-                    of 3 batches of back-to-back steps)
+  depth_device, depth_sah, depth_host     as vrhip_bvh_info reports them
+  mpaths_device_tree, mpaths_sah_tree, mpaths_host_tree    frames-per-step
+                    render rate of the scene on each tree, measured as
+                    scripts/ab.py does (median of 3 batches of back-to-back
+                    steps); sah_rate_vs_host and sah_rate_vs_morton are ratios
+                    of rates from this run
 """
 import argparse
 import json
@@ -27,7 +33,7 @@ sys.path.insert(0, REPO)
 import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
-from vrenderer_pathtracer_amd import VRendererHIP, build_flat, scenes  # noqa: E402
+from vrenderer_pathtracer_amd import VRendererHIP, _native, build_flat, scenes  # noqa: E402
 
 
 def median(v):
@@ -72,35 +78,50 @@ def measure(cfg, nu, nv, leaf, frames, steps):
     d["tris"] = torch.from_numpy(np.ascontiguousarray(mesh["tris"], np.int32)).to(dev)
     torch.cuda.synchronize(dev)
 
-    def device_build(r):
-        r.initMeshDevice(d["positions"], d["tris"], d["normals"], d["tangents"], d["uvs"], max_leaf_tris=leaf)
+    def device_build(r, builder="morton"):
+        r.initMeshDevice(d["positions"], d["tris"], d["normals"], d["tangents"], d["uvs"], max_leaf_tris=leaf,
+                         builder=builder)
 
-    builds = []
-    for i in range(6):                                 # the first is the warm-up
-        r = VRendererHIP(0)
-        r.init(sc["width"], sc["height"])
-        t0 = time.perf_counter()
-        device_build(r)
-        builds.append(time.perf_counter() - t0)
-        depth_dev = r.bvh_info()[0]
-        r.cleanUp()
+    builds, depth_dev = {}, {}
+    for builder in ("morton", "sah"):
+        builds[builder] = []
+        for i in range(6):                             # the first is the warm-up
+            r = VRendererHIP(0)
+            r.init(sc["width"], sc["height"])
+            t0 = time.perf_counter()
+            device_build(r, builder)
+            builds[builder].append(time.perf_counter() - t0)
+            depth_dev[builder] = r.bvh_info()[0]
+            r.cleanUp()
 
     r = VRendererHIP(0)
     scenes.load_into(r, sc)
     rate_host = render_rate(r, sc, frames, steps)
     r.cleanUp()
-    r = VRendererHIP(0)
-    scenes.load_into(r, sc)
-    device_build(r)
-    rate_dev = render_rate(r, sc, frames, steps)
-    r.cleanUp()
-    return {"scene": cfg, "knot": [nu, nv], "n_tris": int(len(mesh["tris"])), "max_leaf_tris": leaf,
-            "device_build_ms": round(median(builds[1:]) * 1e3, 3),
-            "device_build_ms_all": [round(b * 1e3, 3) for b in builds[1:]],
+    rate = {}
+    for builder in ("morton", "sah"):
+        r = VRendererHIP(0)
+        scenes.load_into(r, sc)
+        device_build(r, builder)
+        rate[builder] = render_rate(r, sc, frames, steps)
+        r.cleanUp()
+    n_tris = int(len(mesh["tris"]))
+    arena = int(_native.lib().vrhip_device_sah_scratch_bytes(n_tris))
+    sah_ms = median(builds["sah"][1:]) * 1e3
+    return {"scene": cfg, "knot": [nu, nv], "n_tris": n_tris, "max_leaf_tris": leaf,
+            "device_build_ms": round(median(builds["morton"][1:]) * 1e3, 3),
+            "device_build_ms_all": [round(b * 1e3, 3) for b in builds["morton"][1:]],
+            "sah_build_ms": round(sah_ms, 3), "sah_build_ms_all": [round(b * 1e3, 3) for b in builds["sah"][1:]],
             "host_build_flat_ms": round(host_build * 1e3, 3), "host_init_mesh_ms": round(host_init * 1e3, 3),
-            "depth_device": depth_dev, "depth_host": depth_host, "frames_per_step": frames,
-            "mpaths_device_tree": round(rate_dev, 1), "mpaths_host_tree": round(rate_host, 1),
-            "render_rate_ratio": round(rate_dev / rate_host, 4)}
+            "sah_build_vs_host": round(sah_ms / ((host_build + host_init) * 1e3), 5),
+            "sah_arena_bytes": arena, "sah_arena_bytes_per_tri": round(arena / n_tris, 1),
+            "depth_device": depth_dev["morton"], "depth_sah": depth_dev["sah"], "depth_host": depth_host,
+            "frames_per_step": frames,
+            "mpaths_device_tree": round(rate["morton"], 1), "mpaths_sah_tree": round(rate["sah"], 1),
+            "mpaths_host_tree": round(rate_host, 1),
+            "render_rate_ratio": round(rate["morton"] / rate_host, 4),
+            "sah_rate_vs_host": round(rate["sah"] / rate_host, 4),
+            "sah_rate_vs_morton": round(rate["sah"] / rate["morton"], 4)}
 
 
 def main():

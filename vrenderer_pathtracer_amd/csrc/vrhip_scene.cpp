@@ -12,6 +12,7 @@
 #include "vr_bvh.hpp"
 #include "vr_ctx.hpp"
 #include "vr_devbvh.hpp"
+#include "vr_devsah.hpp"
 #include "vr_exr.hpp"
 #include "vr_merl.hpp"
 #include "vr_mesh_layout.hpp"
@@ -313,12 +314,26 @@ int vrhip_upload_mesh_device(vrhip_ctx* c, const float* d_positions, const float
                              const float* d_uvs, uint32_t n_verts, const uint32_t* d_tris, uint32_t n_tris,
                              uint32_t max_leaf_tris)
 {
+    return vrhip_upload_mesh_device_ex(c, d_positions, d_normals, d_tangents, d_uvs, n_verts, d_tris, n_tris,
+                                       max_leaf_tris, VRHIP_DEVBVH_MORTON);
+}
+
+// builder: the Morton tree of vr_devbvh.hip (its shape is closed-form, so the
+// arrays are sized exactly) or the host's binned-SAH tree of vr_devsah.hip
+// (sized for the worst case of n_refs - 1 nodes; the build reports its shape).
+int vrhip_upload_mesh_device_ex(vrhip_ctx* c, const float* d_positions, const float* d_normals,
+                                const float* d_tangents, const float* d_uvs, uint32_t n_verts, const uint32_t* d_tris,
+                                uint32_t n_tris, uint32_t max_leaf_tris, uint32_t builder)
+{
     if (!c) return fail(VRHIP_ERR_INVALID, "null ctx");
     if (!d_positions || !d_tris || n_tris == 0 || n_verts == 0) return fail(VRHIP_ERR_INVALID, "null or empty mesh arrays");
     if (n_tris >= (1u << (31 - vr::kLeafCountBits))) return fail(VRHIP_ERR_INVALID, "more than 16M triangles");
     if (max_leaf_tris >= (1u << vr::kLeafCountBits)) return fail(VRHIP_ERR_INVALID, "max_leaf_tris above 127");
+    if (builder != VRHIP_DEVBVH_MORTON && builder != VRHIP_DEVBVH_SAH) return fail(VRHIP_ERR_INVALID, "unknown device builder");
     if (!c->group.empty()) return refuse_multi(c, "vrhip_upload_mesh_device");
-    const vr::DevBuildShape sh = vr::devbvh_shape(n_tris, max_leaf_tris ? max_leaf_tris : 2u);
+    const bool sah = builder == VRHIP_DEVBVH_SAH;
+    vr::DevBuildShape sh = vr::devbvh_shape(n_tris, max_leaf_tris ? max_leaf_tris : 2u);
+    if (sah) sh.nodes = sh.n_refs - 1u;           // the worst case: one triangle per leaf
     int rc = set_device(c); if (rc) return rc;
     quiesce(c);
     DeviceBuild b;
@@ -333,15 +348,20 @@ int vrhip_upload_mesh_device(vrhip_ctx* c, const float* d_positions, const float
     HIP_TRY(hipMalloc((void**)&b.o.uvs, nv * 8));
     HIP_TRY(hipMalloc((void**)&b.status, sizeof(vr::DevBuildStatus)));
     HIP_TRY(hipMemsetAsync(b.status, 0, sizeof(vr::DevBuildStatus), c->stream));
-    const int e = vr::devbvh_build(d_positions, d_normals, d_tangents, d_uvs, n_verts, d_tris, n_tris,
-                                   max_leaf_tris ? max_leaf_tris : 2u, b.o, b.status, &b.scratch, c->stream);
+    const int e = (sah ? vr::devsah_build : vr::devbvh_build)(d_positions, d_normals, d_tangents, d_uvs, n_verts, d_tris,
+                                                              n_tris, max_leaf_tris ? max_leaf_tris : 2u, b.o, b.status,
+                                                              &b.scratch, c->stream);
     if (e) return fail(VRHIP_ERR_HIP, std::string("device BVH build: ") + hipGetErrorString((hipError_t)e));
     vr::DevBuildStatus st{};
     HIP_TRY(hipMemcpyAsync(&st, b.status, sizeof(st), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     if (st.flags & vr::DEVBVH_BAD_INDEX) return fail(VRHIP_ERR_INVALID, "a triangle index is >= n_verts");
     if (st.flags & vr::DEVBVH_NONFINITE) return fail(VRHIP_ERR_INVALID, "a referenced vertex position is not finite");
-    if (st.depth != sh.depth || st.nodes != sh.nodes || st.leaves != sh.leaves || st.depth > 62)
+    if (st.flags & vr::DEVBVH_BIG_LEAF) return fail(VRHIP_ERR_BVH, "leaf with >= 128 triangles");
+    if (st.flags) return fail(VRHIP_ERR_BVH, "device BVH build: internal inconsistency");
+    if (sah ? (st.nodes == 0 || st.nodes > sh.nodes || st.leaves != st.nodes + 1u || st.depth == 0 ||
+               st.depth > vr::kMaxBuildDepth)
+            : (st.depth != sh.depth || st.nodes != sh.nodes || st.leaves != sh.leaves || st.depth > 62))
         return fail(VRHIP_ERR_BVH, "device BVH build: the tree is not the shape its size gives");
     dfree(c->bvh); dfree(c->bvh16); dfree(c->verts); dfree(c->tri_e); dfree(c->tpath);
     dfree(c->normals); dfree(c->tangents); dfree(c->uvs);
@@ -355,6 +375,8 @@ int vrhip_upload_mesh_device(vrhip_ctx* c, const float* d_positions, const float
     c->mesh = true;
     return VRHIP_OK;
 }
+
+size_t vrhip_device_sah_scratch_bytes(uint32_t n_tris) { return vr::devsah_arena_bytes(n_tris); }
 
 // The resident mesh back in the reference layout: the LIFO flatten of
 // vr::build_flat over the device tree, so the result does not depend on the

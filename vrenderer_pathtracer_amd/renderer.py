@@ -232,15 +232,26 @@ class VRendererHIP:
                                                fptr(arrs["tangents"]), fptr(arrs["uvs"]),
                                                arrs["verts"].size // 4), "vrhip_upload_mesh_flat")
 
-    def initMeshDevice(self, positions, tris, normals=None, tangents=None, uvs=None, max_leaf_tris: int = 2) -> None:
+    DEVICE_BUILDERS = {"morton": 0, "sah": 1}          # vrhip_device_builder
+
+    def initMeshDevice(self, positions, tris, normals=None, tangents=None, uvs=None, max_leaf_tris: int = 2,
+                       builder="morton") -> None:
         """Build the mesh BVH on the GPU from torch tensors that live on the
-        renderer's device (vrhip_upload_mesh_device): positions, normals,
+        renderer's device (vrhip_upload_mesh_device_ex): positions, normals,
         tangents (N,3) float32, uvs (N,2) float32, tris (M,3) int32 or uint32,
-        all contiguous; the optional arrays default to zeros.  ValueError for
-        a wrong device, dtype or layout.  Synchronises torch's current stream
-        on that device first (the build runs on the renderer's own stream)."""
+        all contiguous; the optional arrays default to zeros.  builder:
+        "morton" (the cheapest build) or "sah" (the tree build_flat makes on
+        the host, built on the device: dearer to build, faster to render).
+        ValueError for a wrong device, dtype or layout, or an unknown builder
+        name (an integer is passed to the library as it is).  Synchronises
+        torch's current stream on that device first (the build runs on the
+        renderer's own stream)."""
         import torch
         self._need_ctx()
+        if isinstance(builder, str):
+            if builder not in self.DEVICE_BUILDERS:
+                raise ValueError(f"builder: {builder!r} (expected 'morton' or 'sah')")
+            builder = self.DEVICE_BUILDERS[builder]
         if isinstance(self._device, (list, tuple)):
             dev = int(self._device[0])
         else:
@@ -271,8 +282,8 @@ class VRendererHIP:
         p_tan = ptr("tangents", tangents, 3, (torch.float32,), nv)
         p_uvs = ptr("uvs", uvs, 2, (torch.float32,), nv)
         torch.cuda.current_stream(dev).synchronize()
-        check(self._lib.vrhip_upload_mesh_device(self._ctx, p_pos, p_nrm, p_tan, p_uvs, nv, p_tri, nt,
-                                                 int(max_leaf_tris)), "vrhip_upload_mesh_device")
+        check(self._lib.vrhip_upload_mesh_device_ex(self._ctx, p_pos, p_nrm, p_tan, p_uvs, nv, p_tri, nt,
+                                                    int(max_leaf_tris), int(builder)), "vrhip_upload_mesh_device")
 
     def export_mesh_flat(self) -> dict:
         """The resident mesh in the reference layout (vrhip_export_mesh_flat):
