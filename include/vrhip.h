@@ -176,6 +176,46 @@ int vrhip_upload_mesh_device_ex(vrhip_ctx *ctx, const float *d_positions, const 
 /* Bytes of device scratch a VRHIP_DEVBVH_SAH build of n_tris triangles takes
  * while it runs (freed before the call returns); 0 without a device. */
 size_t vrhip_device_sah_scratch_bytes(uint32_t n_tris);
+/* New vertex positions for the resident mesh under an unchanged tree: a refit
+ * (no reference counterpart), for a mesh that deforms from step to step.  The
+ * resident mesh must have come from vrhip_upload_mesh_device or
+ * vrhip_upload_mesh_device_ex, with either builder.  Topology stays exactly as
+ * built: triangle indices, leaf membership, node numbering and order, the
+ * triangles' root paths and the uvs.  All pointers are device pointers on the
+ * context's device: d_positions float[3*n_verts], n_verts the upload's.
+ * d_normals and d_tangents may each be NULL, and NULL here means KEEP what is
+ * resident -- unlike the upload calls, where NULL means zeros.  After the
+ * call the vertices (and the triangle test's precomputed edges, the same fp32
+ * subtractions the build makes), and the normals / tangents where given, hold
+ * the new data in the same slots; every child box is the exact fp32 min/max
+ * box of the triangles beneath it, and every fp16 box its outward rounding, as
+ * the builders write them.  Nodes are NOT re-sorted by area, so the kernels'
+ * cached top of the tree may no longer hold the largest boxes: this changes
+ * the rate only, never a result.  A refit tree degrades as the deformation
+ * grows; vrhip_bvh_sah_cost is the number to decide on a rebuild with.
+ * The work runs on the context stream and the call returns when it has
+ * finished.  It does not clear the accumulation, as no upload does (call
+ * vrhip_clear).  Transactional: a read-only pass first checks every referenced
+ * position, and nothing resident is written unless it is clean.
+ * VRHIP_ERR_INVALID (before any device call) for a null ctx or d_positions, no
+ * resident mesh, a mesh from vrhip_upload_mesh_flat / _indexed (it keeps no
+ * index data), n_verts different from the upload's, a vrhip_create_multi
+ * context; and for a non-finite referenced position (found on the device).
+ * Added without an ABI version change (ABI 6 gained this symbol,
+ * vrhip_bvh_sah_cost and vrhip_flat_sah_cost and changed no other). */
+int vrhip_refit_mesh_device(vrhip_ctx *ctx, const float *d_positions, const float *d_normals,
+                            const float *d_tangents, uint32_t n_verts);
+/* SAH cost of the resident tree, whichever call uploaded it, with the
+ * builder's constants (1 per node, 1 per triangle):
+ *   (sum over inner nodes of area(own box)
+ *    + sum over leaves of area(leaf box) * triangle count) / area(root box),
+ * area = dx*dy + dy*dz + dz*dx in fp64 from the fp32 boxes, a node's own box
+ * the union of its two child boxes, the root included in the first sum.
+ * Computed on the device in a fixed order (per-block partials, then one
+ * block): two calls return the same bits.  +infinity (and VRHIP_OK) when the
+ * root's area is 0 or not finite.  VRHIP_ERR_INVALID with no mesh loaded.
+ * Synchronous. */
+int vrhip_bvh_sah_cost(vrhip_ctx *ctx, double *cost);
 /* The resident mesh, whichever upload call brought it, rewritten on the host
  * in the reference layout vrhip_upload_mesh_flat takes (what the oracle, or a
  * caller caching a tree, needs of a device-built tree).  Nodes are numbered
@@ -346,8 +386,8 @@ int vrhip_set_overlap(vrhip_ctx *ctx, int mode);
  *   vrhip_sync, vrhip_read_accum/rgba8/depth8, vrhip_device_buffers,
  *   vrhip_gl_present, vrhip_pack_tiles/unpack_tiles, vrhip_last_kernel_ms,
  *   vrhip_kernel_stats, vrhip_debug_counters, vrhip_set_camera, vrhip_clear,
- *   every upload (vrhip_upload_mesh_device too), vrhip_export_mesh_flat,
- *   vrhip_set_stream, vrhip_set_tiling, vrhip_set_service
+ *   every upload (vrhip_upload_mesh_device too), vrhip_refit_mesh_device,
+ *   vrhip_bvh_sah_cost, vrhip_export_mesh_flat, vrhip_set_stream, vrhip_set_tiling, vrhip_set_service
  *   (and its timing / budget hooks), vrhip_comm_init/destroy, vrhip_destroy,
  *   the counting renders, and a vrhip_render that does not fit the session.
  *   Calls that do NOT close it: the flag setters (Cornell box, example sphere,
@@ -523,6 +563,12 @@ int vrhip_build_flat(const float *positions, const float *normals, const float *
 /* Check a flattened tree; returns VRHIP_OK and its depth / inner-node count. */
 int vrhip_validate_flat(const float *bvh, size_t n_bvh_f4, const float *verts, size_t n_slots,
                         uint32_t *depth, uint32_t *n_nodes);
+/* vrhip_bvh_sah_cost's definition evaluated on the host over a flattened tree
+ * (checked first as vrhip_validate_flat does: VRHIP_ERR_BVH if malformed); a
+ * leaf's triangle count is its run of triples up to the terminator.  The
+ * yardstick for the device value, and the cost of a cached tree without a GPU. */
+int vrhip_flat_sah_cost(const float *bvh, size_t n_bvh_f4, const float *verts, size_t n_slots,
+                        double *cost);
 
 #ifdef __cplusplus
 }

@@ -20,6 +20,14 @@ in scene C5):
                     scripts/ab.py does (median of 3 batches of back-to-back
                     steps); sah_rate_vs_host and sah_rate_vs_morton are ratios
                     of rates from this run
+  refit_ms          median of 5 refits (refitMeshDevice) of the SAH tree to the
+                    deformed knot after one warm-up, same clock; refit_below_sah_build
+                    is the one condition: below sah_build_ms of this run
+  deformations      per twist k (deform below): bvh_sah_cost and the render rate
+                    on (a) the SAH tree built on the undeformed knot and refit,
+                    (b) a SAH tree and (c) a Morton tree rebuilt on the deformed
+                    positions, and the rate ratios (a)/(b), (a)/(c)
+--refit-out writes the refit keys of each line to a second file.
 """
 import argparse
 import json
@@ -54,6 +62,20 @@ def render_rate(r, sc, frames, steps):
         ts.append((time.perf_counter() - t0) / steps)
     paths = (sc["width"] // 16) * 16 * (sc["height"] // 16) * 16 * 2 * frames
     return paths / median(ts) / 1e6
+
+
+def deform(P, k=0.03, shift=(12, -8, 5)):
+    """Twist about y by k*y rad, then shift (tests/test_gpu_refit.py): the knot
+    spans about +-50 and the camera sits at z = 150, so it stays in view."""
+    P = np.asarray(P, np.float64)
+    a = k * P[:, 1]
+    c, s = np.cos(a), np.sin(a)
+    out = np.stack([c * P[:, 0] + s * P[:, 2], P[:, 1], -s * P[:, 0] + c * P[:, 2]], -1)
+    return (out + np.asarray(shift, np.float64)).astype(np.float32)
+
+
+REFIT_KEYS = ("scene", "knot", "n_tris", "max_leaf_tris", "device_build_ms", "sah_build_ms", "refit_ms", "refit_ms_all",
+              "refit_below_sah_build", "refit_vs_sah_build", "refit_vs_morton_build", "frames_per_step", "deformations")
 
 
 def measure(cfg, nu, nv, leaf, frames, steps):
@@ -105,6 +127,39 @@ def measure(cfg, nu, nv, leaf, frames, steps):
         device_build(r, builder)
         rate[builder] = render_rate(r, sc, frames, steps)
         r.cleanUp()
+    # refit: the SAH tree built on the undeformed knot, moved to the deformed one
+    moved = {k: torch.from_numpy(deform(mesh["positions"], k)).to(dev) for k in (0.03, 0.003)}
+    torch.cuda.synchronize(dev)
+    r = VRendererHIP(0)
+    r.init(sc["width"], sc["height"])
+    device_build(r, "sah")
+    refits = []
+    for i in range(6):                                 # the first is the warm-up
+        t0 = time.perf_counter()
+        r.refitMeshDevice(moved[0.03])
+        refits.append(time.perf_counter() - t0)
+    r.cleanUp()
+    deformations = []
+    for k, pos in moved.items():
+        row = {"k": k}
+        for key, builder, refit in (("refit_sah", "sah", True), ("rebuilt_sah", "sah", False),
+                                    ("rebuilt_morton", "morton", False)):
+            r = VRendererHIP(0)
+            scenes.load_into(r, sc)
+            if refit:
+                device_build(r, builder)
+                r.refitMeshDevice(pos)
+            else:
+                r.initMeshDevice(pos, d["tris"], d["normals"], d["tangents"], d["uvs"], max_leaf_tris=leaf,
+                                 builder=builder)
+            r.clearBuffer()
+            row["sah_cost_" + key] = round(r.bvh_sah_cost(), 4)
+            row["mpaths_" + key] = round(render_rate(r, sc, frames, steps), 1)
+            r.cleanUp()
+        row["refit_rate_vs_rebuilt_sah"] = round(row["mpaths_refit_sah"] / row["mpaths_rebuilt_sah"], 4)
+        row["refit_rate_vs_rebuilt_morton"] = round(row["mpaths_refit_sah"] / row["mpaths_rebuilt_morton"], 4)
+        deformations.append(row)
+    refit_ms = median(refits[1:]) * 1e3
     n_tris = int(len(mesh["tris"]))
     arena = int(_native.lib().vrhip_device_sah_scratch_bytes(n_tris))
     sah_ms = median(builds["sah"][1:]) * 1e3
@@ -121,19 +176,30 @@ def measure(cfg, nu, nv, leaf, frames, steps):
             "mpaths_host_tree": round(rate_host, 1),
             "render_rate_ratio": round(rate["morton"] / rate_host, 4),
             "sah_rate_vs_host": round(rate["sah"] / rate_host, 4),
-            "sah_rate_vs_morton": round(rate["sah"] / rate["morton"], 4)}
+            "sah_rate_vs_morton": round(rate["sah"] / rate["morton"], 4),
+            "refit_ms": round(refit_ms, 3), "refit_ms_all": [round(b * 1e3, 3) for b in refits[1:]],
+            "refit_below_sah_build": bool(refit_ms < sah_ms), "refit_vs_sah_build": round(refit_ms / sah_ms, 4),
+            "refit_vs_morton_build": round(refit_ms / (median(builds["morton"][1:]) * 1e3), 4),
+            "deformations": deformations}
 
 
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=None, help="also write the lines to this file")
+    ap.add_argument("--refit-out", default=None, help="write the refit keys of each line to this file")
     ap.add_argument("--frames", type=int, default=16)
     ap.add_argument("--steps", type=int, default=4)
     a = ap.parse_args()
-    lines = []
+    lines, refit_lines = [], []
     for cfg, nu, nv, leaf in (("C2", 100, 50, 2), ("C5", 1000, 500, 4)):
-        lines.append(json.dumps(measure(cfg, nu, nv, leaf, a.frames, a.steps)))
+        m = measure(cfg, nu, nv, leaf, a.frames, a.steps)
+        lines.append(json.dumps(m))
+        refit_lines.append(json.dumps({k: m[k] for k in REFIT_KEYS}))
         print(lines[-1], flush=True)
+    if a.refit_out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.refit_out)), exist_ok=True)
+        with open(a.refit_out, "w") as f:
+            f.write("\n".join(refit_lines) + "\n")
     if a.out:
         os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
         with open(a.out, "w") as f:

@@ -59,6 +59,9 @@ _SIGNATURES = {
     "vrhip_upload_mesh_device_ex": (ctypes.c_int, [_ctx, _vp, _vp, _vp, _vp, ctypes.c_uint32, _vp, ctypes.c_uint32,
                                                    ctypes.c_uint32, ctypes.c_uint32]),
     "vrhip_device_sah_scratch_bytes": (ctypes.c_size_t, [ctypes.c_uint32]),
+    "vrhip_refit_mesh_device": (ctypes.c_int, [_ctx, _vp, _vp, _vp, ctypes.c_uint32]),
+    "vrhip_bvh_sah_cost": (ctypes.c_int, [_ctx, ctypes.POINTER(ctypes.c_double)]),
+    "vrhip_flat_sah_cost": (ctypes.c_int, [_f, ctypes.c_size_t, _f, ctypes.c_size_t, ctypes.POINTER(ctypes.c_double)]),
     "vrhip_export_mesh_flat": (ctypes.c_int, [_ctx, _f, _sz, _f, _f, _f, _f, _sz]),
     "vrhip_upload_hdr": (ctypes.c_int, [_ctx, _f, ctypes.c_uint32, ctypes.c_uint32]),
     "vrhip_upload_hdr_half": (ctypes.c_int, [_ctx, _u16, ctypes.c_uint32, ctypes.c_uint32]),

@@ -584,4 +584,35 @@ int validate_flat(const float* bvh, size_t n_bvh_f4, const float* verts, size_t 
     return 0;
 }
 
+double flat_sah_cost(const float* bvh, const float* verts)
+{
+    auto area = [](const float lo[3], const float hi[3]) {
+        const double dx = (double)hi[0] - (double)lo[0], dy = (double)hi[1] - (double)lo[1],
+                     dz = (double)hi[2] - (double)lo[2];
+        return dx * dy + dy * dz + dz * dx;
+    };
+    double sum = 0.0, root = 0.0;
+    std::vector<size_t> st{ 0 };                                // node float4 offsets
+    while (!st.empty()) {
+        const size_t off = st.back();
+        st.pop_back();
+        const float* n = bvh + 4 * off;
+        const float lo[2][3] = { { n[0], n[2], n[8] }, { n[4], n[6], n[10] } };
+        const float hi[2][3] = { { n[1], n[3], n[9] }, { n[5], n[7], n[11] } };
+        float olo[3], ohi[3];
+        for (int k = 0; k < 3; ++k) { olo[k] = std::min(lo[0][k], lo[1][k]); ohi[k] = std::max(hi[0][k], hi[1][k]); }
+        const double own = area(olo, ohi);
+        if (off == 0) root = own;
+        sum += own;
+        for (int c = 0; c < 2; ++c) {
+            const int32_t idx = fbits(n[12 + c]);
+            if (idx >= 0) { st.push_back((size_t)idx); continue; }
+            size_t s = (size_t)(~idx), count = 0;
+            while ((uint32_t)fbits(verts[4 * s]) != 0x80000000u) { s += 3; ++count; }
+            sum += area(lo[c], hi[c]) * (double)count;
+        }
+    }
+    return root > 0.0 && root < (double)INFINITY ? sum / root : (double)INFINITY;
+}
+
 } // namespace vr

@@ -27,4 +27,11 @@ int build_flat(const float* positions, const float* normals, const float* tangen
 int validate_flat(const float* bvh, size_t n_bvh_f4, const float* verts, size_t n_slots,
                   uint32_t* depth, uint32_t* n_nodes);
 
+// SAH cost of a flattened tree that validate_flat accepted, with the builder's
+// constants (1 per node, 1 per triangle): (sum over inner nodes of the area of
+// their own box + sum over leaves of the area of their box x their triangle
+// count) / the root's area; area = dx dy + dy dz + dz dx in fp64 from the fp32
+// boxes.  +infinity when the root's area is 0 or not finite.
+double flat_sah_cost(const float* bvh, const float* verts);
+
 } // namespace vr

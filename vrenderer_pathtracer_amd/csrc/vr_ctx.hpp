@@ -17,6 +17,7 @@
 #include <vector>
 
 #include "../../include/vrhip.h"
+#include "vr_devbvh.hpp"
 #include "vr_params.hpp"
 
 using vr::vr3;
@@ -67,6 +68,13 @@ struct vrhip_ctx {
     size_t n_bvh = 0, n_slots = 0;
     uint32_t bvh_depth = 0, bvh_nodes = 0, dev_nodes = 0, dev_tris = 0;
     bool mesh = false;
+    // what a device build leaves for vrhip_refit_mesh_device (null after a host
+    // upload): the caller's vertex index behind each compact vertex slot
+    // (uint32[3 dev_tris]), each node's level in the emitted order
+    // (uint32[dev_nodes], the root 0), the build's status record (reused for
+    // the refit's validation flags) and the upload's n_verts
+    uint32_t* slot_vert = nullptr; uint32_t* node_level = nullptr; vr::DevBuildStatus* refit_status = nullptr;
+    uint32_t refit_verts = 0;
     // environment / textures / brdf
     vr4* hdr = nullptr; uint32_t hdr_w = 0, hdr_h = 0;
     vr4* tex[3] = { nullptr, nullptr, nullptr }; uint32_t tex_w[3] = { 0, 0, 0 }, tex_h[3] = { 0, 0, 0 };

@@ -25,6 +25,7 @@
 #include <rocprim/device/device_radix_sort.hpp>
 
 #include "vr_devbvh.hpp"
+#include "vr_refit.hpp"
 
 namespace vr {
 namespace {
@@ -303,7 +304,8 @@ __global__ __launch_bounds__(kBlock) void emit_tris_kernel(const float* __restri
                                                            const uint32_t* __restrict__ sorted, uint32_t n_refs,
                                                            vr3* __restrict__ verts, vr3* __restrict__ tri_e,
                                                            vr4* __restrict__ normals, vr4* __restrict__ tangents,
-                                                           vr2* __restrict__ uvs, const DevBuildStatus* st)
+                                                           vr2* __restrict__ uvs, uint32_t* __restrict__ slot_vert,
+                                                           const DevBuildStatus* st)
 {
     const uint32_t k = blockIdx.x * kBlock + threadIdx.x;
     if (k >= n_refs || st->flags != 0u) return;
@@ -314,6 +316,7 @@ __global__ __launch_bounds__(kBlock) void emit_tris_kernel(const float* __restri
         const size_t o = 3 * (size_t)k + v;
         p[v] = vr3{ pos[3 * i], pos[3 * i + 1], pos[3 * i + 2] };
         verts[o] = p[v];
+        slot_vert[o] = (uint32_t)i;
         normals[o] = nrm ? vr4{ nrm[3 * i], nrm[3 * i + 1], nrm[3 * i + 2], 0.f } : vr4{ 0.f, 0.f, 0.f, 0.f };
         tangents[o] = tan ? vr4{ tan[3 * i], tan[3 * i + 1], tan[3 * i + 2], 0.f } : vr4{ 0.f, 0.f, 0.f, 0.f };
         uvs[o] = uv ? vr2{ uv[2 * i], uv[2 * i + 1] } : vr2{ 0.f, 0.f };
@@ -428,8 +431,10 @@ int devbvh_build(const float* positions, const float* normals, const float* tang
     emit_nodes_kernel<<<blocks_for(N), kBlock, 0, s>>>(N, n, L, order, newpos, child, leafbox, nodebox,
                                                        (float4*)out.bvh, (uint4*)out.bvh16, d_status);
     emit_tris_kernel<<<blocks_for(n), kBlock, 0, s>>>(positions, normals, tangents, uvs, tris, sorted, n, out.verts,
-                                                      out.tri_e, out.normals, out.tangents, out.uvs, d_status);
+                                                      out.tri_e, out.normals, out.tangents, out.uvs, out.slot_vert,
+                                                      d_status);
     if ((e = hipGetLastError()) != hipSuccess) return bail(e);
+    if ((e = (hipError_t)refit_levels(out.bvh, N, sh.depth, out.node_level, s)) != hipSuccess) return bail(e);
     *scratch_out = ar.base;
     return 0;
 }

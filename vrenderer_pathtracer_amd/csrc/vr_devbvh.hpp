@@ -78,10 +78,13 @@ inline DevBuildShape devbvh_shape(uint32_t n_tris, uint32_t max_leaf)
 
 // the eight arrays of the device mesh, allocated by the caller for `shape`:
 // bvh float4[4 nodes], bvh16 float4[2 nodes], verts / tri_e vr3[3 n_refs],
-// tpath u64[n_refs], normals / tangents float4[3 n_refs], uvs vr2[3 n_refs]
+// tpath u64[n_refs], normals / tangents float4[3 n_refs], uvs vr2[3 n_refs];
+// and what a refit needs (vr_refit.hpp): slot_vert u32[3 n_refs], the caller's
+// vertex index behind each compact vertex slot, and node_level u32[nodes], each
+// node's level in the emitted order (the root 0; refit_levels)
 struct DevBuildOut {
     vr4* bvh; vr4* bvh16; vr3* verts; vr3* tri_e; unsigned long long* tpath;
-    vr4* normals; vr4* tangents; vr2* uvs;
+    vr4* normals; vr4* tangents; vr2* uvs; uint32_t* slot_vert; uint32_t* node_level;
 };
 
 // Enqueues the whole build on `stream`.  All pointers are device pointers;

@@ -36,6 +36,7 @@
 #include <rocprim/device/device_scan.hpp>
 
 #include "vr_devsah.hpp"
+#include "vr_refit.hpp"
 
 namespace vr {
 namespace {
@@ -583,7 +584,8 @@ __global__ __launch_bounds__(kBlock) void sah_emit_tris_kernel(const float* __re
                                                                const uint32_t* __restrict__ refs, uint32_t n_refs,
                                                                vr3* __restrict__ verts, vr3* __restrict__ tri_e,
                                                                vr4* __restrict__ normals, vr4* __restrict__ tangents,
-                                                               vr2* __restrict__ uvs, const DevBuildStatus* st)
+                                                               vr2* __restrict__ uvs, uint32_t* __restrict__ slot_vert,
+                                                               const DevBuildStatus* st)
 {
     const uint32_t k = blockIdx.x * kBlock + threadIdx.x;
     if (k >= n_refs || st->flags != 0u) return;
@@ -595,6 +597,7 @@ __global__ __launch_bounds__(kBlock) void sah_emit_tris_kernel(const float* __re
         const size_t o = 3 * (size_t)k + v;
         p[v] = vr3{ pos[3 * i], pos[3 * i + 1], pos[3 * i + 2] };
         verts[o] = p[v];
+        slot_vert[o] = (uint32_t)i;
         normals[o] = nrm ? vr4{ nrm[3 * i], nrm[3 * i + 1], nrm[3 * i + 2], 0.f } : vr4{ 0.f, 0.f, 0.f, 0.f };
         tangents[o] = tan ? vr4{ tan[3 * i], tan[3 * i + 1], tan[3 * i + 2], 0.f } : vr4{ 0.f, 0.f, 0.f, 0.f };
         uvs[o] = uv ? vr2{ uv[2 * i], uv[2 * i + 1] } : vr2{ 0.f, 0.f };
@@ -770,8 +773,10 @@ int devsah_build(const float* positions, const float* normals, const float* tang
     sah_emit_nodes_kernel<<<blocks_for(N), kBlock, 0, s>>>(N, n, depth, sc.order, sc.newpos, sc.child, sc.cbox,
                                                            (float4*)out.bvh, (uint4*)out.bvh16, d_status);
     sah_emit_tris_kernel<<<nb, kBlock, 0, s>>>(positions, normals, tangents, uvs, tris, n_tris, sc.refs[cur], n,
-                                               out.verts, out.tri_e, out.normals, out.tangents, out.uvs, d_status);
+                                               out.verts, out.tri_e, out.normals, out.tangents, out.uvs, out.slot_vert,
+                                               d_status);
     if ((e = hipGetLastError()) != hipSuccess) return bail(e);
+    if ((e = (hipError_t)refit_levels(out.bvh, N, depth, out.node_level, s)) != hipSuccess) return bail(e);
     *scratch_out = ar.base;
     return 0;
 }

@@ -1,0 +1,255 @@
+// vr_refit.hip -- refit of a device-built mesh and the tree's SAH cost
+// (gfx950), declared in vr_refit.hpp.
+//
+// The tree keeps its topology; only what depends on the vertex positions is
+// rewritten, over the arrays the render kernels read:
+//   1. a read-only pass over the positions behind the compact slots (flags
+//      into the status record, as the builders' validation);
+//   2. one thread per compact triangle gathers its vertices through
+//      slot_vert and writes verts and tri_e (normals, tangents where given);
+//   3. the boxes, one launch per level of the emitted node array, deepest
+//      first: a leaf child's box from its triangles' new vertices, an inner
+//      child's box from the two boxes in that child's row, which an earlier
+//      launch has already rewritten.  A thread writes its own row only.
+// Kernel boundaries order every read after the write it needs, so no
+// workgroup waits for another and no result depends on scheduling (the only
+// atomic is the OR of the validation flags).
+#include <hip/hip_runtime.h>
+
+#include "vr_refit.hpp"
+
+namespace vr {
+namespace {
+
+constexpr int kBlock = 256;                       // four wave64
+constexpr uint32_t kLeafCountMask = (1u << kLeafCountBits) - 1u;
+
+inline uint32_t blocks_for(size_t n) { return (uint32_t)((n + kBlock - 1) / kBlock); }
+
+struct Box { float lo[3], hi[3]; };
+
+__device__ __forceinline__ Box empty_box()
+{
+    const float inf = __builtin_inff();
+    return { { inf, inf, inf }, { -inf, -inf, -inf } };
+}
+__device__ __forceinline__ void grow(Box& b, float x, float y, float z)
+{
+    b.lo[0] = fminf(b.lo[0], x); b.lo[1] = fminf(b.lo[1], y); b.lo[2] = fminf(b.lo[2], z);
+    b.hi[0] = fmaxf(b.hi[0], x); b.hi[1] = fmaxf(b.hi[1], y); b.hi[2] = fmaxf(b.hi[2], z);
+}
+
+// the union of the two child boxes in a node's row: the node's own box
+__device__ __forceinline__ Box own_box(const float4* bvh, size_t node)
+{
+    const float4 r0 = bvh[4 * node], r1 = bvh[4 * node + 1], r2 = bvh[4 * node + 2];
+    return { { fminf(r0.x, r1.x), fminf(r0.z, r1.z), fminf(r2.x, r2.z) },
+             { fmaxf(r0.y, r1.y), fmaxf(r0.w, r1.w), fmaxf(r2.y, r2.w) } };
+}
+
+__device__ __forceinline__ bool finite3(float x, float y, float z)
+{
+    const float big = 3.402823466e38f;
+    return fabsf(x) <= big && fabsf(y) <= big && fabsf(z) <= big;      // false for inf and NaN
+}
+
+// ---- the level of every node ---------------------------------------------------
+__global__ __launch_bounds__(kBlock) void refit_level_kernel(const float4* __restrict__ bvh, uint32_t n_nodes,
+                                                             uint32_t d, uint32_t* level)
+{
+    const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
+    if (i >= n_nodes) return;
+    if (d == 0u) {                                // level[] comes filled with ~0: only the root's thread goes on
+        if (i != 0u) return;
+        level[0] = 0u;
+    } else if (level[i] != d) {
+        return;
+    }
+    const float4 r3 = bvh[4 * (size_t)i + 3];
+    const int32_t c[2] = { __float_as_int(r3.x), __float_as_int(r3.y) };
+    for (int ch = 0; ch < 2; ++ch)
+        if (c[ch] > 0 && (uint32_t)c[ch] / 4u < n_nodes) level[(uint32_t)c[ch] / 4u] = d + 1u;
+}
+
+// ---- 1. validation ----------------------------------------------------------------
+__global__ __launch_bounds__(kBlock) void refit_validate_kernel(const float* __restrict__ pos, uint32_t n_verts,
+                                                                const uint32_t* __restrict__ slot_vert, size_t n_slots,
+                                                                DevBuildStatus* st)
+{
+    const size_t s = (size_t)blockIdx.x * kBlock + threadIdx.x;
+    if (s >= n_slots) return;
+    const uint32_t v = slot_vert[s];
+    uint32_t flags = 0u;
+    if (v >= n_verts) flags = DEVBVH_BAD_INDEX;
+    else if (!finite3(pos[3 * (size_t)v], pos[3 * (size_t)v + 1], pos[3 * (size_t)v + 2])) flags = DEVBVH_NONFINITE;
+    if (flags) atomicOr(&st->flags, flags);
+}
+
+// ---- 2. triangles -----------------------------------------------------------------
+__global__ __launch_bounds__(kBlock) void refit_tris_kernel(const float* __restrict__ pos, const float* __restrict__ nrm,
+                                                            const float* __restrict__ tan,
+                                                            const uint32_t* __restrict__ slot_vert, uint32_t n_refs,
+                                                            vr3* __restrict__ verts, vr3* __restrict__ tri_e,
+                                                            vr4* __restrict__ normals, vr4* __restrict__ tangents)
+{
+    const uint32_t k = blockIdx.x * kBlock + threadIdx.x;
+    if (k >= n_refs) return;
+    vr3 p[3];
+    for (int v = 0; v < 3; ++v) {
+        const size_t o = 3 * (size_t)k + v;
+        const size_t i = slot_vert[o];
+        p[v] = vr3{ pos[3 * i], pos[3 * i + 1], pos[3 * i + 2] };
+        verts[o] = p[v];
+        if (nrm) normals[o] = vr4{ nrm[3 * i], nrm[3 * i + 1], nrm[3 * i + 2], 0.f };
+        if (tan) tangents[o] = vr4{ tan[3 * i], tan[3 * i + 1], tan[3 * i + 2], 0.f };
+    }
+    // the Moller-Trumbore edges, the fp32 subtractions of emit_tris_kernel (no contraction possible)
+    tri_e[3 * (size_t)k + 0] = p[0];
+    tri_e[3 * (size_t)k + 1] = vr3{ p[1].x - p[0].x, p[1].y - p[0].y, p[1].z - p[0].z };
+    tri_e[3 * (size_t)k + 2] = vr3{ p[2].x - p[0].x, p[2].y - p[0].y, p[2].z - p[0].z };
+}
+
+// ---- 3. boxes, one launch per level -------------------------------------------------
+// bvh is read (the children's rows, one level down) and written (the thread's
+// own row) in the same launch: never the same row, so no restrict on it
+__global__ __launch_bounds__(kBlock) void refit_boxes_kernel(uint32_t n_nodes, uint32_t n_refs, uint32_t d,
+                                                             const uint32_t* __restrict__ level,
+                                                             const vr3* __restrict__ verts, float4* bvh,
+                                                             uint4* __restrict__ bvh16)
+{
+    const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
+    if (i >= n_nodes || level[i] != d) return;
+    const float4 r3 = bvh[4 * (size_t)i + 3];
+    const int32_t c[2] = { __float_as_int(r3.x), __float_as_int(r3.y) };
+    Box b[2];
+    for (int ch = 0; ch < 2; ++ch) {
+        if (c[ch] < 0) {
+            const uint32_t code = (uint32_t)~c[ch];
+            const uint32_t first = code >> kLeafCountBits, count = code & kLeafCountMask;
+            if (count == 0u || (size_t)first + count > n_refs) return;     // not a tree the builders emit
+            b[ch] = empty_box();
+            for (size_t s = 3 * (size_t)first; s < 3 * ((size_t)first + count); ++s) {
+                const vr3 p = verts[s];
+                grow(b[ch], p.x, p.y, p.z);
+            }
+        } else {
+            const uint32_t j = (uint32_t)c[ch] / 4u;
+            if (j == 0u || j >= n_nodes) return;
+            b[ch] = own_box(bvh, j);
+        }
+    }
+    bvh[4 * (size_t)i + 0] = make_float4(b[0].lo[0], b[0].hi[0], b[0].lo[1], b[0].hi[1]);
+    bvh[4 * (size_t)i + 1] = make_float4(b[1].lo[0], b[1].hi[0], b[1].lo[1], b[1].hi[1]);
+    bvh[4 * (size_t)i + 2] = make_float4(b[0].lo[2], b[0].hi[2], b[1].lo[2], b[1].hi[2]);
+    // the fp16 rows of emit_nodes_kernel: [c0 x y z | c1 x] [c1 y z | idx0 idx1], lows down, highs up
+    auto pair = [](float lo, float hi) {
+        return (uint32_t)half_directed(__float_as_uint(lo), false) |
+               ((uint32_t)half_directed(__float_as_uint(hi), true) << 16);
+    };
+    bvh16[2 * (size_t)i + 0] = make_uint4(pair(b[0].lo[0], b[0].hi[0]), pair(b[0].lo[1], b[0].hi[1]),
+                                          pair(b[0].lo[2], b[0].hi[2]), pair(b[1].lo[0], b[1].hi[0]));
+    bvh16[2 * (size_t)i + 1] = make_uint4(pair(b[1].lo[1], b[1].hi[1]), pair(b[1].lo[2], b[1].hi[2]), (uint32_t)c[0],
+                                          (uint32_t)c[1]);
+}
+
+// ---- SAH cost -----------------------------------------------------------------------
+__device__ __forceinline__ double area64(const float lo[3], const float hi[3])
+{
+    const double dx = (double)hi[0] - (double)lo[0], dy = (double)hi[1] - (double)lo[1],
+                 dz = (double)hi[2] - (double)lo[2];
+    return dx * dy + dy * dz + dz * dx;
+}
+
+// sum of the block's values in a fixed order, valid in thread 0
+__device__ __forceinline__ double block_sum(double v)
+{
+    __shared__ double part[kBlock];
+    part[threadIdx.x] = v;
+    __syncthreads();
+    for (int o = kBlock / 2; o > 0; o >>= 1) {
+        if ((int)threadIdx.x < o) part[threadIdx.x] += part[threadIdx.x + o];
+        __syncthreads();
+    }
+    return part[0];
+}
+
+// per node: the area of its own box, and of each leaf child's box once per triangle
+__global__ __launch_bounds__(kBlock) void refit_cost_kernel(const float4* __restrict__ bvh, uint32_t n_nodes,
+                                                            double* __restrict__ partial)
+{
+    const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
+    double term = 0.0;
+    if (i < n_nodes) {
+        const float4 r0 = bvh[4 * (size_t)i], r1 = bvh[4 * (size_t)i + 1], r2 = bvh[4 * (size_t)i + 2],
+                     r3 = bvh[4 * (size_t)i + 3];
+        const float lo[2][3] = { { r0.x, r0.z, r2.x }, { r1.x, r1.z, r2.z } };
+        const float hi[2][3] = { { r0.y, r0.w, r2.y }, { r1.y, r1.w, r2.w } };
+        const float olo[3] = { fminf(lo[0][0], lo[1][0]), fminf(lo[0][1], lo[1][1]), fminf(lo[0][2], lo[1][2]) };
+        const float ohi[3] = { fmaxf(hi[0][0], hi[1][0]), fmaxf(hi[0][1], hi[1][1]), fmaxf(hi[0][2], hi[1][2]) };
+        term = area64(olo, ohi);
+        const int32_t c[2] = { __float_as_int(r3.x), __float_as_int(r3.y) };
+        for (int ch = 0; ch < 2; ++ch)
+            if (c[ch] < 0) term += area64(lo[ch], hi[ch]) * (double)((uint32_t)~c[ch] & kLeafCountMask);
+    }
+    term = block_sum(term);
+    if (threadIdx.x == 0) partial[blockIdx.x] = term;
+}
+
+__global__ __launch_bounds__(kBlock) void refit_cost_final_kernel(const float4* __restrict__ bvh,
+                                                                  const double* __restrict__ partial,
+                                                                  uint32_t n_partial, double* __restrict__ cost)
+{
+    double sum = 0.0;
+    for (uint32_t i = threadIdx.x; i < n_partial; i += kBlock) sum += partial[i];
+    sum = block_sum(sum);
+    if (threadIdx.x != 0) return;
+    const Box root = own_box(bvh, 0);
+    const double a = area64(root.lo, root.hi);
+    *cost = a > 0.0 && a < (double)__builtin_inff() ? sum / a : (double)__builtin_inff();
+}
+
+} // namespace
+
+int refit_levels(const vr4* bvh, uint32_t n_nodes, uint32_t depth, uint32_t* level, void* stream)
+{
+    hipStream_t s = (hipStream_t)stream;
+    const hipError_t e = hipMemsetAsync(level, 0xff, (size_t)n_nodes * sizeof(uint32_t), s);
+    if (e != hipSuccess) return (int)e;
+    // launch d marks the nodes of level d + 1; the deepest level, depth - 1, has no inner children
+    for (uint32_t d = 0; d == 0u || d + 1u < depth; ++d)
+        refit_level_kernel<<<blocks_for(n_nodes), kBlock, 0, s>>>((const float4*)bvh, n_nodes, d, level);
+    return (int)hipGetLastError();
+}
+
+int refit_validate(const float* positions, uint32_t n_verts, const uint32_t* slot_vert, uint32_t n_refs,
+                   DevBuildStatus* st, void* stream)
+{
+    const size_t n_slots = 3 * (size_t)n_refs;
+    refit_validate_kernel<<<blocks_for(n_slots), kBlock, 0, (hipStream_t)stream>>>(positions, n_verts, slot_vert,
+                                                                                   n_slots, st);
+    return (int)hipGetLastError();
+}
+
+int refit_apply(const float* positions, const float* normals, const float* tangents, const RefitMesh& m, void* stream)
+{
+    hipStream_t s = (hipStream_t)stream;
+    refit_tris_kernel<<<blocks_for(m.n_refs), kBlock, 0, s>>>(positions, normals, tangents, m.slot_vert, m.n_refs,
+                                                              m.verts, m.tri_e, m.normals, m.tangents);
+    for (uint32_t d = m.depth; d-- > 0u;)
+        refit_boxes_kernel<<<blocks_for(m.n_nodes), kBlock, 0, s>>>(m.n_nodes, m.n_refs, d, m.level, m.verts,
+                                                                    (float4*)m.bvh, (uint4*)m.bvh16);
+    return (int)hipGetLastError();
+}
+
+uint32_t refit_cost_blocks(uint32_t n_nodes) { return blocks_for(n_nodes); }
+
+int refit_sah_cost(const vr4* bvh, uint32_t n_nodes, double* partial, double* cost, void* stream)
+{
+    hipStream_t s = (hipStream_t)stream;
+    const uint32_t nb = blocks_for(n_nodes);
+    refit_cost_kernel<<<nb, kBlock, 0, s>>>((const float4*)bvh, n_nodes, partial);
+    refit_cost_final_kernel<<<1, kBlock, 0, s>>>((const float4*)bvh, partial, nb, cost);
+    return (int)hipGetLastError();
+}
+
+} // namespace vr

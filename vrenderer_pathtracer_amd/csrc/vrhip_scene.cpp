@@ -16,6 +16,7 @@
 #include "vr_exr.hpp"
 #include "vr_merl.hpp"
 #include "vr_mesh_layout.hpp"
+#include "vr_refit.hpp"
 
 namespace {
 
@@ -161,6 +162,7 @@ int vrhip_destroy(vrhip_ctx* c)
     quiesce(c);
     dfree(c->accum); dfree(c->rgba); dfree(c->depth); dfree(c->cam_sxy);
     dfree(c->bvh); dfree(c->bvh16); dfree(c->verts); dfree(c->tri_e); dfree(c->tpath); dfree(c->normals); dfree(c->tangents); dfree(c->uvs);
+    dfree(c->slot_vert); dfree(c->node_level); dfree(c->refit_status);
     dfree(c->hdr); dfree(c->tex[0]); dfree(c->tex[1]); dfree(c->tex[2]); dfree(c->brdf);
     for (int i = 0; i < 2; ++i)
         if (c->gl_res[i]) (void)hipGraphicsUnregisterResource(c->gl_res[i]);
@@ -271,6 +273,9 @@ int one_upload_mesh_flat(vrhip_ctx* c, const float* bvh, size_t n_bvh_f4, const 
     if ((rc = upload(c, c->tangents, dm.tangents.data(), nt * 16))) return rc;
     if ((rc = upload(c, c->uvs, dm.uvs.data(), nt * 8))) return rc;
     HIP_TRY(hipStreamSynchronize(c->stream));
+    // a host upload keeps no index data: nothing to refit (vrhip_refit_mesh_device)
+    dfree(c->slot_vert); dfree(c->node_level); dfree(c->refit_status);
+    c->refit_verts = 0;
     c->n_bvh = n_bvh_f4; c->n_slots = n_slots;
     c->bvh_depth = depth; c->bvh_nodes = nodes;
     c->dev_nodes = (uint32_t)(dm.nodes.size() / 4);
@@ -304,7 +309,7 @@ struct DeviceBuild {
     ~DeviceBuild()
     {
         dfree(o.bvh); dfree(o.bvh16); dfree(o.verts); dfree(o.tri_e); dfree(o.tpath);
-        dfree(o.normals); dfree(o.tangents); dfree(o.uvs); dfree(status);
+        dfree(o.normals); dfree(o.tangents); dfree(o.uvs); dfree(o.slot_vert); dfree(o.node_level); dfree(status);
         if (scratch) (void)hipFree(scratch);
     }
 };
@@ -346,6 +351,8 @@ int vrhip_upload_mesh_device_ex(vrhip_ctx* c, const float* d_positions, const fl
     HIP_TRY(hipMalloc((void**)&b.o.normals, nv * 16));
     HIP_TRY(hipMalloc((void**)&b.o.tangents, nv * 16));
     HIP_TRY(hipMalloc((void**)&b.o.uvs, nv * 8));
+    HIP_TRY(hipMalloc((void**)&b.o.slot_vert, nv * sizeof(uint32_t)));
+    HIP_TRY(hipMalloc((void**)&b.o.node_level, (size_t)sh.nodes * sizeof(uint32_t)));
     HIP_TRY(hipMalloc((void**)&b.status, sizeof(vr::DevBuildStatus)));
     HIP_TRY(hipMemsetAsync(b.status, 0, sizeof(vr::DevBuildStatus), c->stream));
     const int e = (sah ? vr::devsah_build : vr::devbvh_build)(d_positions, d_normals, d_tangents, d_uvs, n_verts, d_tris,
@@ -365,9 +372,13 @@ int vrhip_upload_mesh_device_ex(vrhip_ctx* c, const float* d_positions, const fl
         return fail(VRHIP_ERR_BVH, "device BVH build: the tree is not the shape its size gives");
     dfree(c->bvh); dfree(c->bvh16); dfree(c->verts); dfree(c->tri_e); dfree(c->tpath);
     dfree(c->normals); dfree(c->tangents); dfree(c->uvs);
+    dfree(c->slot_vert); dfree(c->node_level); dfree(c->refit_status);
     c->bvh = b.o.bvh; c->bvh16 = b.o.bvh16; c->verts = b.o.verts; c->tri_e = b.o.tri_e; c->tpath = b.o.tpath;
     c->normals = b.o.normals; c->tangents = b.o.tangents; c->uvs = b.o.uvs;
+    c->slot_vert = b.o.slot_vert; c->node_level = b.o.node_level; c->refit_status = b.status;
+    c->refit_verts = n_verts;
     b.o = vr::DevBuildOut{};
+    b.status = nullptr;
     c->n_bvh = 4 * (size_t)st.nodes; c->n_slots = st.slots;
     c->bvh_depth = st.depth; c->bvh_nodes = st.nodes;
     c->dev_nodes = st.nodes;
@@ -377,6 +388,65 @@ int vrhip_upload_mesh_device_ex(vrhip_ctx* c, const float* d_positions, const fl
 }
 
 size_t vrhip_device_sah_scratch_bytes(uint32_t n_tris) { return vr::devsah_arena_bytes(n_tris); }
+
+// New vertex positions under the resident tree (vr_refit.hip): a read-only
+// validation pass and its read-back first, so a refused call writes nothing.
+int vrhip_refit_mesh_device(vrhip_ctx* c, const float* d_positions, const float* d_normals, const float* d_tangents,
+                            uint32_t n_verts)
+{
+    if (!c) return fail(VRHIP_ERR_INVALID, "null ctx");
+    if (!d_positions) return fail(VRHIP_ERR_INVALID, "null positions");
+    if (!c->group.empty()) return refuse_multi(c, "vrhip_refit_mesh_device");
+    if (!c->mesh || c->dev_nodes == 0) return fail(VRHIP_ERR_INVALID, "no mesh loaded");
+    if (!c->slot_vert || !c->node_level || !c->refit_status)
+        return fail(VRHIP_ERR_INVALID, "the resident mesh was not built on the device (it keeps no index data)");
+    if (n_verts != c->refit_verts)
+        return fail(VRHIP_ERR_INVALID, "n_verts is " + std::to_string(n_verts) + ", the upload's was " +
+                                           std::to_string(c->refit_verts));
+    int rc = set_device(c); if (rc) return rc;
+    quiesce(c);
+    HIP_TRY(hipMemsetAsync(c->refit_status, 0, sizeof(vr::DevBuildStatus), c->stream));
+    int e = vr::refit_validate(d_positions, n_verts, c->slot_vert, c->dev_tris, c->refit_status, c->stream);
+    if (e) return fail(VRHIP_ERR_HIP, std::string("mesh refit: ") + hipGetErrorString((hipError_t)e));
+    vr::DevBuildStatus st{};
+    HIP_TRY(hipMemcpyAsync(&st, c->refit_status, sizeof(st), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    if (st.flags & vr::DEVBVH_NONFINITE) return fail(VRHIP_ERR_INVALID, "a referenced vertex position is not finite");
+    if (st.flags) return fail(VRHIP_ERR_BVH, "mesh refit: internal inconsistency");
+    const vr::RefitMesh m{ c->bvh, c->bvh16, c->verts, c->tri_e, c->normals, c->tangents, c->slot_vert, c->node_level,
+                           c->dev_tris, c->dev_nodes, c->bvh_depth };
+    e = vr::refit_apply(d_positions, d_normals, d_tangents, m, c->stream);
+    if (e) return fail(VRHIP_ERR_HIP, std::string("mesh refit: ") + hipGetErrorString((hipError_t)e));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return VRHIP_OK;
+}
+
+int vrhip_bvh_sah_cost(vrhip_ctx* c, double* cost)
+{
+    if (!c || !cost) return fail(VRHIP_ERR_INVALID, "null argument");
+    if (!c->mesh || c->dev_nodes == 0) return fail(VRHIP_ERR_INVALID, "no mesh loaded");
+    int rc = set_device(c); if (rc) return rc;
+    if ((rc = svc_close(c)) != VRHIP_OK) return rc;
+    const uint32_t nb = vr::refit_cost_blocks(c->dev_nodes);
+    double* buf = nullptr;                        // the block partials, then the result
+    HIP_TRY(hipMalloc((void**)&buf, ((size_t)nb + 1) * sizeof(double)));
+    const int e = vr::refit_sah_cost(c->bvh, c->dev_nodes, buf, buf + nb, c->stream);
+    hipError_t he = e ? (hipError_t)e : hipMemcpyAsync(cost, buf + nb, sizeof(double), hipMemcpyDeviceToHost, c->stream);
+    if (he == hipSuccess) he = hipStreamSynchronize(c->stream);
+    else (void)hipStreamSynchronize(c->stream);
+    dfree(buf);
+    if (he != hipSuccess) return fail(VRHIP_ERR_HIP, std::string("SAH cost: ") + hipGetErrorString(he));
+    return svc_verify(c);
+}
+
+int vrhip_flat_sah_cost(const float* bvh, size_t n_bvh_f4, const float* verts, size_t n_slots, double* cost)
+{
+    if (!cost) return fail(VRHIP_ERR_INVALID, "cost is NULL");
+    const int v = vr::validate_flat(bvh, n_bvh_f4, verts, n_slots, nullptr, nullptr);
+    if (v != 0) return fail(VRHIP_ERR_BVH, "validation failed (code " + std::to_string(v) + ")");
+    *cost = vr::flat_sah_cost(bvh, verts);
+    return VRHIP_OK;
+}
 
 // The resident mesh back in the reference layout: the LIFO flatten of
 // vr::build_flat over the device tree, so the result does not depend on the

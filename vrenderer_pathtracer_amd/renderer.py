@@ -80,6 +80,19 @@ def validate_flat(flat: dict) -> tuple[int, int]:
     return d.value, n.value
 
 
+def flat_sah_cost(flat: dict) -> float:
+    """SAH cost of a flattened tree over its root's area, on the host
+    (vrhip_flat_sah_cost): the definition VRendererHIP.bvh_sah_cost evaluates
+    on the device.  Raises if the tree is malformed."""
+    L = _native.lib()
+    cost = ctypes.c_double(0.0)
+    bvh = _f32(flat["bvh"])
+    verts = _f32(flat["verts"])
+    check(L.vrhip_flat_sah_cost(fptr(bvh), bvh.size // 4, fptr(verts), verts.size // 4, ctypes.byref(cost)),
+          "vrhip_flat_sah_cost")
+    return cost.value
+
+
 _POWF_LUTS = {}
 
 
@@ -252,27 +265,9 @@ class VRendererHIP:
             if builder not in self.DEVICE_BUILDERS:
                 raise ValueError(f"builder: {builder!r} (expected 'morton' or 'sah')")
             builder = self.DEVICE_BUILDERS[builder]
-        if isinstance(self._device, (list, tuple)):
-            dev = int(self._device[0])
-        else:
-            dev = int(self._device)
+        dev = self._torch_device()
         int_types = tuple(t for t in (torch.int32, getattr(torch, "uint32", None)) if t is not None)
-
-        def ptr(name, t, cols, dtypes, rows=None):
-            if t is None:
-                return None
-            if not isinstance(t, torch.Tensor):
-                raise ValueError(f"{name}: expected a torch tensor")
-            if t.device.type != "cuda" or t.device.index != dev:
-                raise ValueError(f"{name}: tensor is on {t.device}, the renderer on GPU {dev}")
-            if t.dtype not in dtypes:
-                raise ValueError(f"{name}: dtype {t.dtype} (expected {' or '.join(str(d) for d in dtypes)})")
-            if t.dim() != 2 or t.shape[1] != cols or (rows is not None and t.shape[0] != rows):
-                raise ValueError(f"{name}: shape {tuple(t.shape)} (expected ({'N' if rows is None else rows}, {cols}))")
-            if not t.is_contiguous():
-                raise ValueError(f"{name}: tensor is not contiguous")
-            return ctypes.c_void_p(t.data_ptr())
-
+        ptr = self._tensor_ptr
         p_pos = ptr("positions", positions, 3, (torch.float32,))
         p_tri = ptr("tris", tris, 3, int_types)
         if p_pos is None or p_tri is None:
@@ -284,6 +279,60 @@ class VRendererHIP:
         torch.cuda.current_stream(dev).synchronize()
         check(self._lib.vrhip_upload_mesh_device_ex(self._ctx, p_pos, p_nrm, p_tan, p_uvs, nv, p_tri, nt,
                                                     int(max_leaf_tris), int(builder)), "vrhip_upload_mesh_device")
+
+    def refitMeshDevice(self, positions, normals=None, tangents=None) -> None:
+        """Move the vertices of a mesh that initMeshDevice built, keeping its
+        tree (vrhip_refit_mesh_device): positions (N,3) float32 for the N
+        vertices of the upload; normals and tangents (N,3) float32 or None,
+        and None KEEPS the resident ones (initMeshDevice's None means zeros).
+        Tensors as for initMeshDevice (ValueError for a wrong device, dtype,
+        shape or layout); the library's refusals raise VRHIPError and leave
+        the mesh as it was.  Synchronises torch's current stream first.  The
+        accumulation is not cleared (clearBuffer)."""
+        import torch
+        self._need_ctx()
+        dev = self._torch_device()
+        ptr = self._tensor_ptr
+        p_pos = ptr("positions", positions, 3, (torch.float32,))
+        if p_pos is None:
+            raise ValueError("positions are required")
+        nv = int(positions.shape[0])
+        p_nrm = ptr("normals", normals, 3, (torch.float32,), nv)
+        p_tan = ptr("tangents", tangents, 3, (torch.float32,), nv)
+        torch.cuda.current_stream(dev).synchronize()
+        check(self._lib.vrhip_refit_mesh_device(self._ctx, p_pos, p_nrm, p_tan, nv), "vrhip_refit_mesh_device")
+
+    def bvh_sah_cost(self) -> float:
+        """SAH cost of the resident tree over its root's area (vrhip_bvh_sah_cost):
+        what a refit tree is compared by against a rebuilt one."""
+        cost = ctypes.c_double(0.0)
+        check(self._lib.vrhip_bvh_sah_cost(self._need_ctx(), ctypes.byref(cost)), "vrhip_bvh_sah_cost")
+        return cost.value
+
+    def _torch_device(self) -> int:
+        """The GPU index device tensors must live on (a group's first device)."""
+        if isinstance(self._device, (list, tuple)):
+            return int(self._device[0])
+        return int(self._device)
+
+    def _tensor_ptr(self, name, t, cols, dtypes, rows=None):
+        """The device pointer of an (N, cols) torch tensor on the renderer's
+        GPU, or None for None; ValueError for anything else."""
+        import torch
+        dev = self._torch_device()
+        if t is None:
+            return None
+        if not isinstance(t, torch.Tensor):
+            raise ValueError(f"{name}: expected a torch tensor")
+        if t.device.type != "cuda" or t.device.index != dev:
+            raise ValueError(f"{name}: tensor is on {t.device}, the renderer on GPU {dev}")
+        if t.dtype not in dtypes:
+            raise ValueError(f"{name}: dtype {t.dtype} (expected {' or '.join(str(d) for d in dtypes)})")
+        if t.dim() != 2 or t.shape[1] != cols or (rows is not None and t.shape[0] != rows):
+            raise ValueError(f"{name}: shape {tuple(t.shape)} (expected ({'N' if rows is None else rows}, {cols}))")
+        if not t.is_contiguous():
+            raise ValueError(f"{name}: tensor is not contiguous")
+        return ctypes.c_void_p(t.data_ptr())
 
     def export_mesh_flat(self) -> dict:
         """The resident mesh in the reference layout (vrhip_export_mesh_flat):
