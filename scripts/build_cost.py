@@ -36,11 +36,12 @@ import sys
 import time
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, REPO)
+sys.path[:0] = [REPO, os.path.join(REPO, "tests")]
 
 import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
+from device_mesh_cases import deform  # noqa: E402  (the twist of tests/test_gpu_refit.py)
 from vrenderer_pathtracer_amd import VRendererHIP, _native, build_flat, scenes  # noqa: E402
 
 
@@ -62,16 +63,6 @@ def render_rate(r, sc, frames, steps):
         ts.append((time.perf_counter() - t0) / steps)
     paths = (sc["width"] // 16) * 16 * (sc["height"] // 16) * 16 * 2 * frames
     return paths / median(ts) / 1e6
-
-
-def deform(P, k=0.03, shift=(12, -8, 5)):
-    """Twist about y by k*y rad, then shift (tests/test_gpu_refit.py): the knot
-    spans about +-50 and the camera sits at z = 150, so it stays in view."""
-    P = np.asarray(P, np.float64)
-    a = k * P[:, 1]
-    c, s = np.cos(a), np.sin(a)
-    out = np.stack([c * P[:, 0] + s * P[:, 2], P[:, 1], -s * P[:, 0] + c * P[:, 2]], -1)
-    return (out + np.asarray(shift, np.float64)).astype(np.float32)
 
 
 REFIT_KEYS = ("scene", "knot", "n_tris", "max_leaf_tris", "device_build_ms", "sah_build_ms", "refit_ms", "refit_ms_all",

@@ -1,11 +1,11 @@
-// Host driver for vr::half_directed (csrc/vr_devbvh.hpp), the device BVH
+// Host driver for vr::half_directed (csrc/vr_devmesh.hpp), the device BVH
 // builder's outward fp32 -> fp16 rounding: reads float bit patterns (hex, one
 // per line) from stdin and prints "down up" (decimal half bit patterns) for
 // each.  The function is the same source the kernels compile.
 #include <cstdint>
 #include <cstdio>
 
-#include "vr_devbvh.hpp"
+#include "vr_devmesh.hpp"
 
 int main()
 {

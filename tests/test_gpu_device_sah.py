@@ -6,7 +6,9 @@ exported tree, errors are transactional, and the Morton builder is unchanged."""
 import numpy as np
 import pytest
 
+import device_mesh_cases as cases
 import pyoracle as po
+from device_mesh_cases import HARD_KINDS, bitexact, expected_triangles, hard_mesh, sorted_rows, soup
 from vrenderer_pathtracer_amd import VRendererHIP, VRHIPError, build_flat, scenes, validate_flat
 
 pytestmark = pytest.mark.gpu
@@ -16,74 +18,17 @@ T = 64                                                 # kSahSmall (csrc/vr_devs
 MAX_BUILD_DEPTH = 30                                   # kMaxBuildDepth
 
 
-# ---- meshes -----------------------------------------------------------------
-def soup(n, seed=5, spread=30.0, sigma=4.0):
-    """The generator of test_capi.test_random_soup_bvh_equals_brute_force."""
-    rng = np.random.default_rng(seed)
-    c = rng.uniform(-spread, spread, (n, 1, 3))
-    P = (c + rng.normal(0, sigma, (n, 3, 3))).reshape(-1, 3).astype(np.float32)
-    return dict(positions=P, normals=rng.normal(0, 1, (3 * n, 3)).astype(np.float32),
-                tangents=rng.normal(0, 1, (3 * n, 3)).astype(np.float32),
-                uvs=rng.uniform(0, 1, (3 * n, 2)).astype(np.float32),
-                tris=np.arange(3 * n, dtype=np.uint32).reshape(-1, 3))
-
-
-def hard_mesh(kind):
-    """The hard inputs of test_gpu_device_build.py."""
-    if kind == "identical":
-        m = soup(1, seed=2, spread=5.0, sigma=12.0)
-        return {k: np.tile(v, (50, 1)) if k != "tris" else np.arange(150, dtype=np.uint32).reshape(-1, 3)
-                for k, v in m.items()}
-    if kind == "equal_centres":
-        base = np.array([[-1, -1, -1], [1, -1, 1], [0, 1, 0]], np.float32)     # box [-1, 1]^3
-        m = soup(40, seed=3)
-        m["positions"] = np.concatenate([base * np.float32(2.0 + 0.25 * i) for i in range(40)]).astype(np.float32)
-        return m
-    if kind == "zero_area":
-        m = soup(60, seed=4)
-        P = m["positions"].reshape(-1, 3, 3)
-        P[::3, 1] = P[::3, 0]                                                  # two equal vertices
-        P[1::6, 1] = P[1::6, 0]
-        P[1::6, 2] = P[1::6, 0]                                                # a point
-        return m
-    if kind == "flat_axis":
-        m = soup(80, seed=6)
-        m["positions"][:, 2] = 0.0
-        return m
-    if kind == "far":
-        return soup(80, seed=7, spread=1e5, sigma=3e4)
-    if kind == "shared":
-        return scenes.torus_knot(40, 20)
-    if kind == "no_attributes":
-        m = scenes.torus_knot(40, 20)
-        return dict(positions=m["positions"], tris=m["tris"])
-    raise ValueError(kind)
-
-
+# ---- builds: this file's default builder is the SAH one ---------------------------
 def device_build(r, mesh, max_leaf=2, builder="sah", **kw):
-    import torch
-    dev = torch.device("cuda", 0)
-
-    def t(a, dtype):
-        return None if a is None else torch.from_numpy(np.ascontiguousarray(a).astype(dtype)).to(dev)
-    if builder is not None:
-        kw["builder"] = builder
-    r.initMeshDevice(t(mesh["positions"], np.float32), t(mesh["tris"], np.int32), t(mesh.get("normals"), np.float32),
-                     t(mesh.get("tangents"), np.float32), t(mesh.get("uvs"), np.float32), max_leaf_tris=max_leaf, **kw)
-
-
-def fresh(w=64, h=48):
-    r = VRendererHIP(0)
-    r.init(w, h)
-    return r
+    cases.device_build(r, mesh, max_leaf, builder, **kw)
 
 
 def built_export(mesh, max_leaf=2, builder="sah"):
-    r = fresh()
-    device_build(r, mesh, max_leaf, builder)
-    flat, info = r.export_mesh_flat(), r.bvh_info()
-    r.cleanUp()
-    return flat, info
+    return cases.built_export(mesh, max_leaf, builder)
+
+
+def loaded(sc, mesh, builder="sah"):
+    return cases.loaded(sc, mesh, builder)
 
 
 _HOST = {}
@@ -97,18 +42,6 @@ def host_flat(key, mesh, max_leaf):
 
 
 # ---- the exported tree ---------------------------------------------------------
-def expected_triangles(mesh):
-    """Per input triangle, its 3 x (position, normal, tangent, uv) as one row."""
-    tris = np.asarray(mesh["tris"], np.int64)
-    nv = len(mesh["positions"])
-    cols = [np.asarray(mesh["positions"], np.float32)[tris]]
-    for key, k in (("normals", 3), ("tangents", 3), ("uvs", 2)):
-        a = mesh.get(key)
-        a = np.zeros((nv, k), np.float32) if a is None else np.asarray(a, np.float32)
-        cols.append(a[tris])
-    return np.ascontiguousarray(np.concatenate(cols, -1).reshape(len(tris), -1))
-
-
 def slot_rows(flat):
     """(is_term, rows): per non-terminator slot triple, the row expected_triangles gives."""
     verts = flat["verts"]
@@ -123,11 +56,6 @@ def leaf_of_triple(is_term):
     """Per slot triple, the index of its leaf run (runs end at terminators)."""
     run = np.cumsum(is_term) - is_term                 # per slot: terminators before it
     return run[~is_term][::3]
-
-
-def sorted_rows(a):
-    a = np.ascontiguousarray(a, np.float32) + np.float32(0.0)             # -0 -> +0: compare as floats
-    return a[np.lexsort(a.T[::-1])]
 
 
 def check_boxes_and_leaves(flat, mesh, max_leaf):
@@ -153,8 +81,7 @@ def check_boxes_and_leaves(flat, mesh, max_leaf):
         assert counts.max() <= max_leaf, counts.max()
     assert starts[0] == 0 and (starts[1:] == ends[:-1] + 1).all() and ends[-1] == len(verts) - 1
     assert len(verts) == 3 * n_refs + L
-    want = expected_triangles(mesh)
-    want = np.concatenate([want, want]) if n_tris == 1 else want           # one triangle is stored twice
+    want = expected_triangles(mesh)                    # one triangle is stored twice: two rows
     assert np.array_equal(sorted_rows(rows), sorted_rows(want))
     lo_src = np.where(is_term[:, None], np.inf, verts[:, :3]).astype(np.float32)
     hi_src = np.where(is_term[:, None], -np.inf, verts[:, :3]).astype(np.float32)
@@ -247,8 +174,7 @@ def test_single_triangle_sits_under_two_leaves(native, max_leaf):
 
 
 # ---- 2. hard inputs -----------------------------------------------------------
-@pytest.mark.parametrize("kind", ["identical", "equal_centres", "zero_area", "flat_axis", "far", "shared",
-                                  "no_attributes"])
+@pytest.mark.parametrize("kind", HARD_KINDS)
 def test_hard_inputs_valid_and_bitexact(native, oracle, kind):
     mesh = hard_mesh(kind)
     sc = scenes.make_scene("C2", 64, 48)
@@ -271,19 +197,6 @@ def test_hard_inputs_valid_and_bitexact(native, oracle, kind):
 
 
 # ---- 3. render parity -----------------------------------------------------------
-def bitexact(g, o, what):
-    diff = (g.view(np.uint32) != o.view(np.uint32)) if g.dtype == np.float32 else (g != o)
-    n = int(diff.any(-1).sum())
-    assert n == 0, f"{what}: {n} pixels differ (first at {np.argwhere(diff.any(-1))[:3].tolist()})"
-
-
-def loaded(sc, mesh, builder="sah"):
-    r = VRendererHIP(0)
-    scenes.load_into(r, sc)
-    device_build(r, mesh, 2, builder)
-    return r
-
-
 @pytest.mark.parametrize("name", ["C2", "C3"])
 def test_render_parity_on_sah_built_knot(native, oracle, name):
     mesh = scenes.torus_knot(100, 50)

@@ -8,24 +8,13 @@ import numpy as np
 import pytest
 
 import pyoracle as po
-from test_gpu_device_build import bitexact, fresh, soup
-from test_gpu_device_sah import check_boxes_and_leaves, device_build
+from device_mesh_cases import BUILDERS, bitexact, deform, device_build, fresh, loaded, soup
+from test_gpu_device_sah import check_boxes_and_leaves
 from vrenderer_pathtracer_amd import VRendererHIP, VRHIPError, flat_sah_cost, scenes, validate_flat
 
 pytestmark = pytest.mark.gpu
 
 TERM = 0x80000000
-BUILDERS = ["morton", "sah"]
-
-
-def deform(P, k=0.03, shift=(12, -8, 5)):
-    """Twist about y by k*y rad, then shift: float64 math, the result as
-    float32 (the test holds the exact fp32 positions the device gets)."""
-    P = np.asarray(P, np.float64)
-    a = k * P[:, 1]
-    c, s = np.cos(a), np.sin(a)
-    out = np.stack([c * P[:, 0] + s * P[:, 2], P[:, 1], -s * P[:, 0] + c * P[:, 2]], -1)
-    return (out + np.asarray(shift, np.float64)).astype(np.float32)
 
 
 def twist_dirs(D, P, k=0.03):
@@ -42,13 +31,6 @@ def dev(a):
 
 def refit(r, positions, normals=None, tangents=None):
     r.refitMeshDevice(dev(positions), dev(normals), dev(tangents))
-
-
-def loaded(sc, mesh, builder):
-    r = VRendererHIP(0)
-    scenes.load_into(r, sc)
-    device_build(r, mesh, 2, builder)
-    return r
 
 
 def index_words(flat):

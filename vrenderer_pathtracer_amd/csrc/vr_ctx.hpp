@@ -17,7 +17,7 @@
 #include <vector>
 
 #include "../../include/vrhip.h"
-#include "vr_devbvh.hpp"
+#include "vr_devmesh.hpp"
 #include "vr_params.hpp"
 
 using vr::vr3;

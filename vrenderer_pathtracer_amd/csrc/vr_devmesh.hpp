@@ -1,0 +1,103 @@
+// vr_devmesh.hpp -- what the device builders (vr_devbvh.hip, vr_devsah.hip)
+// and the refit (vr_refit.hip) share about the device mesh layout
+// (vr_mesh_layout.hpp DeviceMesh): the status record, the output arrays, the
+// leaf code, the box and the fp16 rounding of the node rows.  Host-compilable:
+// tests/half_driver.cpp and tests/sah_driver.cpp compile this text.  The
+// device side is vr_devmesh_dev.hpp and vr_devmesh.hip.
+#pragma once
+#include <cstddef>
+#include <cstdint>
+
+#include "vr_params.hpp"
+
+namespace vr {
+
+#if defined(__HIPCC__)
+#define VR_DEVBVH_HD __host__ __device__
+#else
+#define VR_DEVBVH_HD
+#endif
+
+// IEEE binary16 bits of the float with bit pattern `bits`, rounded toward
+// +inf (up) or -inf (down); equals half_bits_directed (vr_mesh_layout.cpp) for
+// every non-NaN float (both infinities included; NaN patterns differ, see
+// docs/DESIGN_HISTORY.md).  The magnitude is truncated toward zero and stepped one
+// half ulp outward when that moved it to the wrong side: 0x7bff + 1 is
+// infinity (out of range on the outward side), 0x03ff + 1 the smallest normal.
+VR_DEVBVH_HD inline uint16_t half_directed(uint32_t bits, bool up)
+{
+    const uint32_t sign = (bits >> 16) & 0x8000u;
+    const uint32_t a = bits & 0x7fffffffu;
+    uint32_t mag;
+    bool inexact;
+    if (a >= 0x477fe000u) {                       // |x| >= 65504: the largest finite half
+        mag = 0x7bffu;
+        inexact = a > 0x477fe000u;
+    } else if (a < 0x38800000u) {                 // |x| < 2^-14: half subnormal, |x| * 2^24 truncated
+        const uint32_t e = a >> 23;
+        const uint32_t mant = (a & 0x7fffffu) | 0x800000u;
+        const uint32_t sh = 126u - e;             // >= 14
+        if (e == 0u || sh > 24u) { mag = 0u; inexact = a != 0u; }
+        else { mag = mant >> sh; inexact = (mant & ((1u << sh) - 1u)) != 0u; }
+    } else {                                      // normal: rebias the exponent, keep 10 fraction bits
+        mag = (a - 0x38000000u) >> 13;
+        inexact = (a & 0x1fffu) != 0u;
+    }
+    if (inexact && (up != (sign != 0u))) mag += 1u;   // outward: away from zero on the rounding side
+    return (uint16_t)(sign | mag);
+}
+
+// half_directed on n device floats, both directions (vrhip_selftest_half_box)
+int launch_half_box(const float* in, size_t n, uint16_t* down, uint16_t* up, void* stream);
+
+// errors found on the device (DevBuildStatus::flags)
+enum : uint32_t { DEVBVH_BAD_INDEX = 1u, DEVBVH_NONFINITE = 2u, DEVBVH_BIG_LEAF = 4u, DEVBVH_INTERNAL = 8u };
+
+// the record a build or a refit leaves for the host (one small read-back)
+struct DevBuildStatus {
+    uint32_t flags;      // DEVBVH_*
+    uint32_t depth;      // as validate_flat counts it (root = 1)
+    uint32_t nodes;      // inner nodes
+    uint32_t leaves;
+    uint32_t slots;      // reference slots: 3 per triangle reference + 1 terminator per leaf
+    uint32_t pad[3];
+};
+
+// the eight arrays of the device mesh, allocated by the caller:
+// bvh float4[4 nodes], bvh16 float4[2 nodes], verts / tri_e vr3[3 n_refs],
+// tpath u64[n_refs], normals / tangents float4[3 n_refs], uvs vr2[3 n_refs];
+// and what a refit needs (vr_refit.hpp): slot_vert u32[3 n_refs], the caller's
+// vertex index behind each compact vertex slot, and node_level u32[nodes], each
+// node's level in the emitted order (the root 0; refit_levels)
+struct DevBuildOut {
+    vr4* bvh; vr4* bvh16; vr3* verts; vr3* tri_e; unsigned long long* tpath;
+    vr4* normals; vr4* tangents; vr2* uvs; uint32_t* slot_vert; uint32_t* node_level;
+};
+
+// A leaf child's index word: ~((first << 7) | count) over the compact triangles
+// (vr_kernel.hpp trav_iter reads it); an inner child's is its float4 offset.
+VR_DEVBVH_HD inline bool leaf_count_fits(uint32_t count) { return (count >> kLeafCountBits) == 0u; }
+VR_DEVBVH_HD inline int32_t leaf_code(uint32_t first, uint32_t count)
+{
+    return ~(int32_t)((first << kLeafCountBits) | count);
+}
+VR_DEVBVH_HD inline void leaf_range(int32_t code, uint32_t& first, uint32_t& count)
+{
+    const uint32_t u = (uint32_t)~code;
+    first = u >> kLeafCountBits;
+    count = u & ((1u << kLeafCountBits) - 1u);
+}
+
+// One box layout for every device-side site.  How a box grows is not shared:
+// the SAH builder selects with < and > as the host's Box::grow does
+// (vr_devsah.hpp sah_grow), the Morton builder and the refit use fminf / fmaxf
+// (vr_devmesh_dev.hpp grow_fminmax); the two can differ in the sign of a zero bound.
+struct DevBox { float lo[3], hi[3]; };
+
+VR_DEVBVH_HD inline DevBox empty_box()
+{
+    const float inf = __builtin_inff();
+    return { { inf, inf, inf }, { -inf, -inf, -inf } };
+}
+
+} // namespace vr

@@ -28,20 +28,18 @@
 // One counter is read back per level (the number of splits).  Kernel
 // boundaries give all ordering; no workgroup waits for another.  No result
 // depends on scheduling: the only atomics are integer min, max, add and or.
-// Emission is that of vr_devbvh.hip: the root first, the other nodes by
-// descending area, fp16 rows by half_directed.
+// Emission is the stage shared with the Morton builder (vr_devmesh_dev.hpp
+// emit_mesh): the root first, the other nodes by descending area.
 #include <cstring>                                // rocPRIM's iterators call memset without including it
 #include <hip/hip_runtime.h>
-#include <rocprim/device/device_radix_sort.hpp>
 #include <rocprim/device/device_scan.hpp>
 
+#include "vr_devmesh_dev.hpp"
 #include "vr_devsah.hpp"
-#include "vr_refit.hpp"
 
 namespace vr {
 namespace {
 
-constexpr int kBlock = 256;                       // four wave64
 constexpr int kChunk = 8;                         // references per thread in the bounds and bin kernels
 constexpr uint32_t kInactive = 0xffffffffu;       // a reference whose leaf is made
 constexpr uint32_t kNoAxis = 3u;
@@ -62,11 +60,6 @@ struct Control { uint32_t splits; uint32_t pad[3]; };
 __device__ __forceinline__ int32_t enc(float f) { return sah_ordered(__float_as_int(f)); }
 __device__ __forceinline__ float dec(int32_t i) { return __int_as_float(sah_ordered(i)); }
 
-__device__ __forceinline__ SahBox load_tribox(const float4* a, size_t i)
-{
-    const float4 lo = a[2 * i], hi = a[2 * i + 1];
-    return { { lo.x, lo.y, lo.z }, { hi.x, hi.y, hi.z } };
-}
 __device__ __forceinline__ SahBox centroid_box(const SahBox& t)
 {
     SahBox c;
@@ -93,11 +86,6 @@ __device__ __forceinline__ SahBox wave_union(SahBox b)
     }
     return b;
 }
-__device__ __forceinline__ bool finite3(float x, float y, float z)
-{
-    const float big = 3.402823466e38f;
-    return fabsf(x) <= big && fabsf(y) <= big && fabsf(z) <= big;      // false for inf and NaN
-}
 __device__ __forceinline__ void fail(DevBuildStatus* st) { atomicOr(&st->flags, DEVBVH_INTERNAL); }
 
 // ---- triangle boxes, validation, the first order ------------------------------
@@ -113,23 +101,9 @@ __global__ __launch_bounds__(kBlock) void sah_tris_kernel(const float* __restric
     refs[k] = t;
     node_of[k] = 0u;
     if (k >= n_tris) return;
-    const float inf = __builtin_inff();
-    float4 lo = make_float4(inf, inf, inf, 0.f), hi = make_float4(-inf, -inf, -inf, 0.f);
-    uint32_t flags = 0u;
-    const uint32_t idx[3] = { tris[3 * (size_t)t], tris[3 * (size_t)t + 1], tris[3 * (size_t)t + 2] };
-    if (idx[0] >= n_verts || idx[1] >= n_verts || idx[2] >= n_verts) {
-        flags = DEVBVH_BAD_INDEX;
-    } else {
-        for (int v = 0; v < 3; ++v) {
-            const float* p = pos + 3 * (size_t)idx[v];
-            const float x = p[0], y = p[1], z = p[2];
-            if (!finite3(x, y, z)) flags |= DEVBVH_NONFINITE;
-            lo.x = fminf(lo.x, x); lo.y = fminf(lo.y, y); lo.z = fminf(lo.z, z);
-            hi.x = fmaxf(hi.x, x); hi.y = fmaxf(hi.y, y); hi.z = fmaxf(hi.z, z);
-        }
-    }
-    tribox[2 * (size_t)t] = lo;
-    tribox[2 * (size_t)t + 1] = hi;
+    DevBox b;
+    const uint32_t flags = triangle_box(pos, n_verts, tris, t, b);
+    store_box(tribox, t, b);
     if (flags) atomicOr(&st->flags, flags);
 }
 
@@ -191,7 +165,7 @@ __global__ __launch_bounds__(kBlock) void sah_bounds_kernel(uint32_t n_refs, uin
             if (cur != kInactive) flush_bounds(state, cur, b, cb);
             cur = item; b = sah_empty(); cb = sah_empty();
         }
-        const SahBox t = load_tribox(tribox, refs[i]);
+        const SahBox t = load_box(tribox, refs[i]);
         sah_grow(b, t);
         sah_grow(cb, centroid_box(t));
     }
@@ -245,7 +219,7 @@ __global__ __launch_bounds__(kBlock) void sah_bin_kernel(uint32_t n_refs, uint32
         const uint32_t slot = im.first / (kSahSmall + 1u);
         if (slot >= n_slots) { fail(st); continue; }
         const SahBox cb = dec_box(state[item].cb);
-        const SahBox t = load_tribox(tribox, refs[i]);
+        const SahBox t = load_box(tribox, refs[i]);
         for (int a = 0; a < 3; ++a) {
             const float ext = cb.hi[a] - cb.lo[a];
             if (!(ext > 0.f)) continue;
@@ -329,7 +303,7 @@ __global__ __launch_bounds__(kBlock) void sah_node_kernel(uint32_t n_items, uint
     if (im.count <= kSahSmall) {
         // a reference per lane
         const bool act = (uint32_t)lane < im.count;
-        const SahBox tb = act ? load_tribox(tribox, refs[im.first + lane]) : sah_empty();
+        const SahBox tb = act ? load_box(tribox, refs[im.first + lane]) : sah_empty();
         const SahBox tc = act ? centroid_box(tb) : sah_empty();
         b = wave_union(tb);
         cb = wave_union(tc);
@@ -435,7 +409,7 @@ __global__ __launch_bounds__(kBlock) void sah_flag_kernel(uint32_t n_refs, uint3
         const uint32_t a = state[item].axis;
         if (a < 3u) {
             const float lo = dec(state[item].cb[a]), hi = dec(state[item].cb[3 + a]);
-            const SahBox t = load_tribox(tribox, refs[i]);
+            const SahBox t = load_box(tribox, refs[i]);
             left = sah_bin(sah_centroid(t.lo[a], t.hi[a]), lo, hi - lo) <= (int)state[item].k ? 1u : 0u;
         } else {
             left = i - items[item].first < state[item].nl ? 1u : 0u;
@@ -463,25 +437,22 @@ __global__ __launch_bounds__(kBlock) void sah_children_kernel(uint32_t n_items, 
     const uint32_t which = i & 1u;
     if ((size_t)im.first + im.count > n_refs) { fail(st); return; }
     const SahBox b = dec_box(s.b);
-    const float4 lo = make_float4(b.lo[0], b.lo[1], b.lo[2], 0.f), hi = make_float4(b.hi[0], b.hi[1], b.hi[2], 0.f);
     if (i == n_items - 1u) ctl->splits = sidx[i] + isplit[i];
     if (level > 0u) {
         if (im.parent >= max_nodes) { fail(st); return; }
-        cbox[2 * (2 * (size_t)im.parent + which)] = lo;
-        cbox[2 * (2 * (size_t)im.parent + which) + 1] = hi;
+        store_box(cbox, 2 * (size_t)im.parent + which, b);
     }
     if (s.split) {
         const uint32_t id = node_base + sidx[i];
         if (id >= max_nodes || 2u * sidx[i] + 1u >= n_refs) { fail(st); return; }
-        nodebox[2 * (size_t)id] = lo;
-        nodebox[2 * (size_t)id + 1] = hi;
+        store_box(nodebox, id, b);
         if (level > 0u) child[2 * (size_t)im.parent + which] = (int32_t)id;
         next[2u * sidx[i]] = Item{ im.first, s.nl, id, 0u, sah_child_path(im.path, level, 0u) };
         next[2u * sidx[i] + 1u] = Item{ im.first + s.nl, im.count - s.nl, id, 0u, sah_child_path(im.path, level, 1u) };
     } else {
         if (level == 0u) { fail(st); return; }   // the root is always split
-        if (im.count >= (1u << kLeafCountBits)) { atomicOr(&st->flags, DEVBVH_BIG_LEAF); return; }
-        child[2 * (size_t)im.parent + which] = ~(int32_t)((im.first << kLeafCountBits) | im.count);
+        if (!leaf_count_fits(im.count)) { atomicOr(&st->flags, DEVBVH_BIG_LEAF); return; }
+        child[2 * (size_t)im.parent + which] = leaf_code(im.first, im.count);
         for (uint32_t k = 0; k < im.count; ++k) tpath[im.first + k] = im.path;
     }
 }
@@ -514,122 +485,29 @@ __global__ __launch_bounds__(kBlock) void sah_scatter_kernel(uint32_t n_refs, ui
     node_out[dest] = 2u * sidx[item] + (left ? 0u : 1u);
 }
 
-// ---- node order and emission (as vr_devbvh.hip) -----------------------------------
-__global__ __launch_bounds__(kBlock) void sah_area_keys_kernel(uint32_t n_nodes, const float4* __restrict__ nodebox,
-                                                               unsigned long long* __restrict__ keys,
-                                                               uint32_t* __restrict__ vals)
-{
-    const uint32_t id = blockIdx.x * kBlock + threadIdx.x;
-    if (id >= n_nodes) return;
-    const float4 lo = nodebox[2 * (size_t)id], hi = nodebox[2 * (size_t)id + 1];
-    const float dx = hi.x - lo.x, dy = hi.y - lo.y, dz = hi.z - lo.z;
-    float area = dx * dy + dy * dz + dz * dx;
-    if (!(area >= 0.f)) area = __builtin_inff();  // inf * 0 of an overflowed extent
-    const uint32_t inv = ~__float_as_uint(area);
-    keys[id] = id == 0u ? 0ull : ((unsigned long long)inv << 32) | (id + 1u);       // the root is node 0
-    vals[id] = id;
-}
-
-__global__ __launch_bounds__(kBlock) void sah_newpos_kernel(uint32_t n_nodes, const uint32_t* __restrict__ order,
-                                                            uint32_t* __restrict__ newpos)
-{
-    const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
-    if (i < n_nodes && order[i] < n_nodes) newpos[order[i]] = i;
-}
-
-__global__ __launch_bounds__(kBlock) void sah_emit_nodes_kernel(uint32_t n_nodes, uint32_t n_refs, uint32_t depth,
-                                                                const uint32_t* __restrict__ order,
-                                                                const uint32_t* __restrict__ newpos,
-                                                                const int32_t* __restrict__ child,
-                                                                const float4* __restrict__ cbox,
-                                                                float4* __restrict__ bvh, uint4* __restrict__ bvh16,
-                                                                DevBuildStatus* st)
-{
-    const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
-    if (i == 0u) {
-        st->nodes = n_nodes;
-        st->leaves = n_nodes + 1u;
-        st->slots = 3u * n_refs + n_nodes + 1u;
-        st->depth = depth;
-    }
-    if (i >= n_nodes) return;
-    const uint32_t id = order[i];
-    if (id >= n_nodes) { fail(st); return; }
-    const int32_t c0 = child[2 * (size_t)id], c1 = child[2 * (size_t)id + 1];
-    if ((c0 >= 0 && (uint32_t)c0 >= n_nodes) || (c1 >= 0 && (uint32_t)c1 >= n_nodes)) { fail(st); return; }
-    const float4 l0 = cbox[4 * (size_t)id], h0 = cbox[4 * (size_t)id + 1];
-    const float4 l1 = cbox[4 * (size_t)id + 2], h1 = cbox[4 * (size_t)id + 3];
-    // float4 offsets for inner children, ~((first << 7) | count) for leaves
-    const int32_t i0 = c0 < 0 ? c0 : (int32_t)(4u * newpos[c0]);
-    const int32_t i1 = c1 < 0 ? c1 : (int32_t)(4u * newpos[c1]);
-    bvh[4 * (size_t)i + 0] = make_float4(l0.x, h0.x, l0.y, h0.y);
-    bvh[4 * (size_t)i + 1] = make_float4(l1.x, h1.x, l1.y, h1.y);
-    bvh[4 * (size_t)i + 2] = make_float4(l0.z, h0.z, l1.z, h1.z);
-    bvh[4 * (size_t)i + 3] = make_float4(__int_as_float(i0), __int_as_float(i1), 0.f, 0.f);
-    // the fp16 rows of build_nodes16: [c0 x y z | c1 x] [c1 y z | idx0 idx1], lows down, highs up
-    auto pair = [](float lo, float hi) {
-        return (uint32_t)half_directed(__float_as_uint(lo), false) |
-               ((uint32_t)half_directed(__float_as_uint(hi), true) << 16);
-    };
-    bvh16[2 * (size_t)i + 0] = make_uint4(pair(l0.x, h0.x), pair(l0.y, h0.y), pair(l0.z, h0.z), pair(l1.x, h1.x));
-    bvh16[2 * (size_t)i + 1] = make_uint4(pair(l1.y, h1.y), pair(l1.z, h1.z), (uint32_t)i0, (uint32_t)i1);
-}
-
-// one thread per compact triangle, in the final order of the references
-__global__ __launch_bounds__(kBlock) void sah_emit_tris_kernel(const float* __restrict__ pos,
-                                                               const float* __restrict__ nrm,
-                                                               const float* __restrict__ tan,
-                                                               const float* __restrict__ uv,
-                                                               const uint32_t* __restrict__ tris, uint32_t n_tris,
-                                                               const uint32_t* __restrict__ refs, uint32_t n_refs,
-                                                               vr3* __restrict__ verts, vr3* __restrict__ tri_e,
-                                                               vr4* __restrict__ normals, vr4* __restrict__ tangents,
-                                                               vr2* __restrict__ uvs, uint32_t* __restrict__ slot_vert,
-                                                               const DevBuildStatus* st)
-{
-    const uint32_t k = blockIdx.x * kBlock + threadIdx.x;
-    if (k >= n_refs || st->flags != 0u) return;
-    const uint32_t t = refs[k];
-    if (t >= n_tris) return;
-    vr3 p[3];
-    for (int v = 0; v < 3; ++v) {
-        const size_t i = tris[3 * (size_t)t + v];
-        const size_t o = 3 * (size_t)k + v;
-        p[v] = vr3{ pos[3 * i], pos[3 * i + 1], pos[3 * i + 2] };
-        verts[o] = p[v];
-        slot_vert[o] = (uint32_t)i;
-        normals[o] = nrm ? vr4{ nrm[3 * i], nrm[3 * i + 1], nrm[3 * i + 2], 0.f } : vr4{ 0.f, 0.f, 0.f, 0.f };
-        tangents[o] = tan ? vr4{ tan[3 * i], tan[3 * i + 1], tan[3 * i + 2], 0.f } : vr4{ 0.f, 0.f, 0.f, 0.f };
-        uvs[o] = uv ? vr2{ uv[2 * i], uv[2 * i + 1] } : vr2{ 0.f, 0.f };
-    }
-    // the Moller-Trumbore edges, the kernel's own fp32 subtractions (no contraction possible)
-    tri_e[3 * (size_t)k + 0] = p[0];
-    tri_e[3 * (size_t)k + 1] = vr3{ p[1].x - p[0].x, p[1].y - p[0].y, p[1].z - p[0].z };
-    tri_e[3 * (size_t)k + 2] = vr3{ p[2].x - p[0].x, p[2].y - p[0].y, p[2].z - p[0].z };
-}
-
-inline uint32_t blocks_for(size_t n) { return (uint32_t)((n + kBlock - 1) / kBlock); }
-
-// carves 256-B aligned pieces out of one allocation
-struct Arena {
-    size_t used = 0;
-    char* base = nullptr;
-    template <typename T>
-    T* take(size_t n)
+// ---- emission: this tree's children (vr_devmesh_dev.hpp emit_nodes_kernel) ---------
+struct SahChildren {
+    const int32_t* child;                         // per node, two: a node number or a leaf code
+    const float4* cbox;                           // per node, its two child boxes
+    __device__ bool operator()(uint32_t id, uint32_t n_nodes, DevBox b[2], int32_t c[2], DevBuildStatus* st) const
     {
-        const size_t off = used;
-        used += (n * sizeof(T) + 255u) & ~(size_t)255u;
-        return base ? (T*)(base + off) : nullptr;
+        if (id >= n_nodes) { fail(st); return false; }
+        for (int k = 0; k < 2; ++k) {
+            c[k] = child[2 * (size_t)id + k];
+            if (c[k] >= 0 && (uint32_t)c[k] >= n_nodes) { fail(st); return false; }
+            b[k] = load_box(cbox, 2 * (size_t)id + k);
+        }
+        return true;
     }
 };
 
 struct Scratch {
     float4 *tribox, *nodebox, *cbox;
-    uint32_t *refs[2], *node_of[2], *flags, *rank, *isplit, *sidx, *avals, *order, *newpos;
+    uint32_t *refs[2], *node_of[2], *flags, *rank, *isplit, *sidx;
     Item* items[2];
     ItemState* state;
     int32_t *bins, *child;
-    unsigned long long *akeys, *akeys_sorted;
+    EmitScratch emit;
     Control* ctl;
     char* temp;
     size_t n_slots;
@@ -639,7 +517,6 @@ void carve(Arena& ar, Scratch& s, uint32_t n, size_t temp_bytes)
 {
     const size_t N = n - 1u;                      // nodes at most
     s.n_slots = n / (kSahSmall + 1u) + 1u;        // large items have distinct first / (kSahSmall + 1)
-    ar.used = 0;
     s.tribox = ar.take<float4>(2 * (size_t)n);
     for (int i = 0; i < 2; ++i) {
         s.refs[i] = ar.take<uint32_t>(n);
@@ -655,11 +532,7 @@ void carve(Arena& ar, Scratch& s, uint32_t n, size_t temp_bytes)
     s.nodebox = ar.take<float4>(2 * N);
     s.cbox = ar.take<float4>(4 * N);
     s.child = ar.take<int32_t>(2 * N);
-    s.akeys = ar.take<unsigned long long>(N);
-    s.akeys_sorted = ar.take<unsigned long long>(N);
-    s.avals = ar.take<uint32_t>(N);
-    s.order = ar.take<uint32_t>(N);
-    s.newpos = ar.take<uint32_t>(N);
+    s.emit.carve(ar, N);
     s.ctl = ar.take<Control>(1);
     s.temp = ar.take<char>(temp_bytes ? temp_bytes : 16);
 }
@@ -670,8 +543,7 @@ hipError_t temp_sizes(uint32_t n, hipStream_t s, size_t& bytes)
     hipError_t e = rocprim::exclusive_scan(nullptr, scan, (uint32_t*)nullptr, (uint32_t*)nullptr, 0u, (size_t)n,
                                            rocprim::plus<uint32_t>(), s);
     if (e != hipSuccess) return e;
-    e = rocprim::radix_sort_pairs(nullptr, sort, (unsigned long long*)nullptr, (unsigned long long*)nullptr,
-                                  (uint32_t*)nullptr, (uint32_t*)nullptr, (size_t)(n - 1u), 0u, 64u, s);
+    e = emit_sort_temp_bytes(n - 1u, s, sort);
     bytes = scan > sort ? scan : sort;
     return e;
 }
@@ -703,11 +575,7 @@ int devsah_build(const float* positions, const float* normals, const float* tang
     if (e != hipSuccess) return (int)e;
     Arena ar;
     Scratch sc;
-    carve(ar, sc, n, temp_bytes);                 // sizes first, then pointers
-    void* p = nullptr;
-    if ((e = hipMalloc(&p, ar.used)) != hipSuccess) return (int)e;
-    ar.base = (char*)p;
-    carve(ar, sc, n, temp_bytes);
+    if ((e = carve_alloc(ar, [&](Arena& a) { carve(a, sc, n, temp_bytes); })) != hipSuccess) return (int)e;
     auto bail = [&](hipError_t err) { (void)hipStreamSynchronize(s); (void)hipFree(ar.base); return (int)err; };
 
     const uint32_t nb = blocks_for(n), nb_chunk = (uint32_t)((n + (size_t)kBlock * kChunk - 1) / ((size_t)kBlock * kChunk));
@@ -764,19 +632,9 @@ int devsah_build(const float* positions, const float* normals, const float* tang
     const uint32_t N = node_base;
     if (N == 0u || n_items != 0u) return bail(hipErrorUnknown);
 
-    sah_area_keys_kernel<<<blocks_for(N), kBlock, 0, s>>>(N, sc.nodebox, sc.akeys, sc.avals);
-    if ((e = hipGetLastError()) != hipSuccess) return bail(e);
-    size_t tb = temp_bytes;
-    e = rocprim::radix_sort_pairs(sc.temp, tb, sc.akeys, sc.akeys_sorted, sc.avals, sc.order, (size_t)N, 0u, 64u, s);
-    if (e != hipSuccess) return bail(e);
-    sah_newpos_kernel<<<blocks_for(N), kBlock, 0, s>>>(N, sc.order, sc.newpos);
-    sah_emit_nodes_kernel<<<blocks_for(N), kBlock, 0, s>>>(N, n, depth, sc.order, sc.newpos, sc.child, sc.cbox,
-                                                           (float4*)out.bvh, (uint4*)out.bvh16, d_status);
-    sah_emit_tris_kernel<<<nb, kBlock, 0, s>>>(positions, normals, tangents, uvs, tris, n_tris, sc.refs[cur], n,
-                                               out.verts, out.tri_e, out.normals, out.tangents, out.uvs, out.slot_vert,
-                                               d_status);
-    if ((e = hipGetLastError()) != hipSuccess) return bail(e);
-    if ((e = (hipError_t)refit_levels(out.bvh, N, depth, out.node_level, s)) != hipSuccess) return bail(e);
+    const EmitArgs ea{ N, 0u, N + 1u, depth, true, sc.nodebox, sc.refs[cur], n, n_tris,
+                       { positions, normals, tangents, uvs }, tris, sc.emit, sc.temp, temp_bytes, out, d_status };
+    if ((e = emit_mesh(ea, SahChildren{ sc.child, sc.cbox }, s)) != hipSuccess) return bail(e);
     *scratch_out = ar.base;
     return 0;
 }

@@ -18,7 +18,7 @@
 #include <cstdint>
 
 #include "vr_bvh.hpp"
-#include "vr_devbvh.hpp"
+#include "vr_devmesh.hpp"
 
 namespace vr {
 
@@ -27,16 +27,8 @@ constexpr int kSahBins = 128;                     // vr_bvh.cpp VR_BVH_BINS
 // registers (a lane per reference); larger nodes bin into global memory.
 constexpr uint32_t kSahSmall = 64;
 
-// further DevBuildStatus flags (vr_devbvh.hpp has 1 and 2)
-enum : uint32_t { DEVBVH_BIG_LEAF = 4u, DEVBVH_INTERNAL = 8u };
-
-struct SahBox { float lo[3], hi[3]; };
-
-VR_DEVBVH_HD inline SahBox sah_empty()
-{
-    const float inf = __builtin_inff();
-    return { { inf, inf, inf }, { -inf, -inf, -inf } };
-}
+using SahBox = DevBox;                            // the layout is shared, sah_grow is this builder's own
+VR_DEVBVH_HD inline SahBox sah_empty() { return empty_box(); }
 // Box::grow (vr_bvh.cpp:34-39): componentwise min / max
 VR_DEVBVH_HD inline void sah_grow(SahBox& b, const SahBox& o)
 {

@@ -16,41 +16,17 @@
 // atomic is the OR of the validation flags).
 #include <hip/hip_runtime.h>
 
-#include "vr_refit.hpp"
+#include "vr_devmesh_dev.hpp"
 
 namespace vr {
 namespace {
 
-constexpr int kBlock = 256;                       // four wave64
-constexpr uint32_t kLeafCountMask = (1u << kLeafCountBits) - 1u;
-
-inline uint32_t blocks_for(size_t n) { return (uint32_t)((n + kBlock - 1) / kBlock); }
-
-struct Box { float lo[3], hi[3]; };
-
-__device__ __forceinline__ Box empty_box()
-{
-    const float inf = __builtin_inff();
-    return { { inf, inf, inf }, { -inf, -inf, -inf } };
-}
-__device__ __forceinline__ void grow(Box& b, float x, float y, float z)
-{
-    b.lo[0] = fminf(b.lo[0], x); b.lo[1] = fminf(b.lo[1], y); b.lo[2] = fminf(b.lo[2], z);
-    b.hi[0] = fmaxf(b.hi[0], x); b.hi[1] = fmaxf(b.hi[1], y); b.hi[2] = fmaxf(b.hi[2], z);
-}
-
 // the union of the two child boxes in a node's row: the node's own box
-__device__ __forceinline__ Box own_box(const float4* bvh, size_t node)
+__device__ __forceinline__ DevBox own_box(const float4* bvh, size_t node)
 {
     const float4 r0 = bvh[4 * node], r1 = bvh[4 * node + 1], r2 = bvh[4 * node + 2];
     return { { fminf(r0.x, r1.x), fminf(r0.z, r1.z), fminf(r2.x, r2.z) },
              { fmaxf(r0.y, r1.y), fmaxf(r0.w, r1.w), fmaxf(r2.y, r2.w) } };
-}
-
-__device__ __forceinline__ bool finite3(float x, float y, float z)
-{
-    const float big = 3.402823466e38f;
-    return fabsf(x) <= big && fabsf(y) <= big && fabsf(z) <= big;      // false for inf and NaN
 }
 
 // ---- the level of every node ---------------------------------------------------
@@ -94,19 +70,9 @@ __global__ __launch_bounds__(kBlock) void refit_tris_kernel(const float* __restr
 {
     const uint32_t k = blockIdx.x * kBlock + threadIdx.x;
     if (k >= n_refs) return;
-    vr3 p[3];
-    for (int v = 0; v < 3; ++v) {
-        const size_t o = 3 * (size_t)k + v;
-        const size_t i = slot_vert[o];
-        p[v] = vr3{ pos[3 * i], pos[3 * i + 1], pos[3 * i + 2] };
-        verts[o] = p[v];
-        if (nrm) normals[o] = vr4{ nrm[3 * i], nrm[3 * i + 1], nrm[3 * i + 2], 0.f };
-        if (tan) tangents[o] = vr4{ tan[3 * i], tan[3 * i + 1], tan[3 * i + 2], 0.f };
-    }
-    // the Moller-Trumbore edges, the fp32 subtractions of emit_tris_kernel (no contraction possible)
-    tri_e[3 * (size_t)k + 0] = p[0];
-    tri_e[3 * (size_t)k + 1] = vr3{ p[1].x - p[0].x, p[1].y - p[0].y, p[1].z - p[0].z };
-    tri_e[3 * (size_t)k + 2] = vr3{ p[2].x - p[0].x, p[2].y - p[0].y, p[2].z - p[0].z };
+    const uint32_t vi[3] = { slot_vert[3 * (size_t)k], slot_vert[3 * (size_t)k + 1], slot_vert[3 * (size_t)k + 2] };
+    gather_triangle<false>(TriSource{ pos, nrm, tan, nullptr }, TriArrays{ verts, tri_e, normals, tangents, nullptr, nullptr },
+                           k, vi);
 }
 
 // ---- 3. boxes, one launch per level -------------------------------------------------
@@ -121,16 +87,16 @@ __global__ __launch_bounds__(kBlock) void refit_boxes_kernel(uint32_t n_nodes, u
     if (i >= n_nodes || level[i] != d) return;
     const float4 r3 = bvh[4 * (size_t)i + 3];
     const int32_t c[2] = { __float_as_int(r3.x), __float_as_int(r3.y) };
-    Box b[2];
+    DevBox b[2];
     for (int ch = 0; ch < 2; ++ch) {
         if (c[ch] < 0) {
-            const uint32_t code = (uint32_t)~c[ch];
-            const uint32_t first = code >> kLeafCountBits, count = code & kLeafCountMask;
+            uint32_t first, count;
+            leaf_range(c[ch], first, count);
             if (count == 0u || (size_t)first + count > n_refs) return;     // not a tree the builders emit
             b[ch] = empty_box();
             for (size_t s = 3 * (size_t)first; s < 3 * ((size_t)first + count); ++s) {
                 const vr3 p = verts[s];
-                grow(b[ch], p.x, p.y, p.z);
+                grow_fminmax(b[ch], p.x, p.y, p.z);
             }
         } else {
             const uint32_t j = (uint32_t)c[ch] / 4u;
@@ -138,18 +104,7 @@ __global__ __launch_bounds__(kBlock) void refit_boxes_kernel(uint32_t n_nodes, u
             b[ch] = own_box(bvh, j);
         }
     }
-    bvh[4 * (size_t)i + 0] = make_float4(b[0].lo[0], b[0].hi[0], b[0].lo[1], b[0].hi[1]);
-    bvh[4 * (size_t)i + 1] = make_float4(b[1].lo[0], b[1].hi[0], b[1].lo[1], b[1].hi[1]);
-    bvh[4 * (size_t)i + 2] = make_float4(b[0].lo[2], b[0].hi[2], b[1].lo[2], b[1].hi[2]);
-    // the fp16 rows of emit_nodes_kernel: [c0 x y z | c1 x] [c1 y z | idx0 idx1], lows down, highs up
-    auto pair = [](float lo, float hi) {
-        return (uint32_t)half_directed(__float_as_uint(lo), false) |
-               ((uint32_t)half_directed(__float_as_uint(hi), true) << 16);
-    };
-    bvh16[2 * (size_t)i + 0] = make_uint4(pair(b[0].lo[0], b[0].hi[0]), pair(b[0].lo[1], b[0].hi[1]),
-                                          pair(b[0].lo[2], b[0].hi[2]), pair(b[1].lo[0], b[1].hi[0]));
-    bvh16[2 * (size_t)i + 1] = make_uint4(pair(b[1].lo[1], b[1].hi[1]), pair(b[1].lo[2], b[1].hi[2]), (uint32_t)c[0],
-                                          (uint32_t)c[1]);
+    write_node_rows<false>(bvh, bvh16, i, b[0], b[1], c[0], c[1]);       // the index row stays
 }
 
 // ---- SAH cost -----------------------------------------------------------------------
@@ -184,12 +139,15 @@ __global__ __launch_bounds__(kBlock) void refit_cost_kernel(const float4* __rest
                      r3 = bvh[4 * (size_t)i + 3];
         const float lo[2][3] = { { r0.x, r0.z, r2.x }, { r1.x, r1.z, r2.z } };
         const float hi[2][3] = { { r0.y, r0.w, r2.y }, { r1.y, r1.w, r2.w } };
-        const float olo[3] = { fminf(lo[0][0], lo[1][0]), fminf(lo[0][1], lo[1][1]), fminf(lo[0][2], lo[1][2]) };
-        const float ohi[3] = { fmaxf(hi[0][0], hi[1][0]), fmaxf(hi[0][1], hi[1][1]), fmaxf(hi[0][2], hi[1][2]) };
-        term = area64(olo, ohi);
+        const DevBox own = own_box(bvh, i);
+        term = area64(own.lo, own.hi);
         const int32_t c[2] = { __float_as_int(r3.x), __float_as_int(r3.y) };
-        for (int ch = 0; ch < 2; ++ch)
-            if (c[ch] < 0) term += area64(lo[ch], hi[ch]) * (double)((uint32_t)~c[ch] & kLeafCountMask);
+        for (int ch = 0; ch < 2; ++ch) {
+            if (c[ch] >= 0) continue;
+            uint32_t first, count;
+            leaf_range(c[ch], first, count);
+            term += area64(lo[ch], hi[ch]) * (double)count;
+        }
     }
     term = block_sum(term);
     if (threadIdx.x == 0) partial[blockIdx.x] = term;
@@ -203,7 +161,7 @@ __global__ __launch_bounds__(kBlock) void refit_cost_final_kernel(const float4* 
     for (uint32_t i = threadIdx.x; i < n_partial; i += kBlock) sum += partial[i];
     sum = block_sum(sum);
     if (threadIdx.x != 0) return;
-    const Box root = own_box(bvh, 0);
+    const DevBox root = own_box(bvh, 0);
     const double a = area64(root.lo, root.hi);
     *cost = a > 0.0 && a < (double)__builtin_inff() ? sum / a : (double)__builtin_inff();
 }

@@ -6,7 +6,7 @@
 #include <cstddef>
 #include <cstdint>
 
-#include "vr_devbvh.hpp"
+#include "vr_devmesh.hpp"
 
 namespace vr {
 

@@ -1,7 +1,7 @@
 // vrhip_selftest.cpp -- device self-tests and the vector-memory microbenchmark
 // (vrhip_selftest_*, vrhip_microbench_vmem): no context, a device index only.
 #include "vr_ctx.hpp"
-#include "vr_devbvh.hpp"
+#include "vr_devmesh.hpp"
 
 int vrhip_microbench_vmem(int device, uint32_t width_bytes, uint32_t distinct, double* lane_loads_per_s)
 {
