@@ -224,6 +224,54 @@ int vrhip_bvh_sah_cost(vrhip_ctx *ctx, double *cost);
  * VRHIP_ERR_INVALID with no mesh loaded.  Synchronous. */
 int vrhip_export_mesh_flat(vrhip_ctx *ctx, float *bvh, size_t *n_bvh_f4, float *verts, float *normals,
                            float *tangents, float *uvs, size_t *n_slots);
+/* Ray queries against the resident mesh (no reference counterpart as a call:
+ * the reference traces its own camera and bounce rays only): where does ray i,
+ * origin d_origins[3i..], direction d_dirs[3i..], hit the mesh?  All pointers
+ * are device pointers on the context's device; d_hits is 16-byte aligned.
+ *   What is tested: the resident triangle mesh only.  The Cornell spheres, the
+ *     small spheres and the example sphere are not part of the query, and the
+ *     scene flags (vrhip_use_example_sphere included) have no effect on it.
+ *   The test per triangle is the reference's intersectTriangle
+ *     (cuda/include/RayIntersection.cuh:54-111) and closest-hit update
+ *     (cuda/src/PathTracer.cu:379-386): fp32 without contraction, a hit needs
+ *     dist > 3e-10 and dist < the closest so far (strict).  The closest so far
+ *     starts at d_tmax[i], or at 1e20 (the reference's "no hit" distance) when
+ *     d_tmax is NULL.  Directions are used as given, not normalised: t is in
+ *     units of the direction's length.
+ *   The record: t, the triangle, and the barycentrics u, v of that test.
+ *     `prim` names the triangle in the caller's terms, by how the mesh came:
+ *     vrhip_upload_mesh_device / _ex (also after any refit): the index of the
+ *       triangle in the upload's d_tris;
+ *     vrhip_upload_mesh_flat: the slot of the triangle's first vertex in the
+ *       verts array as uploaded (the reference's own hit index);
+ *     vrhip_upload_mesh_indexed: that slot in the arrays vrhip_build_flat
+ *       returns for the same arguments;
+ *     vrhip_flat_trace_rays: the slot in the arrays it was given.
+ *   Ties: of two triangles hit at exactly the same t the one the reference's
+ *     depth-first walk tests first wins, in both traversal modes
+ *     (vrhip_set_strict_traversal selects the walk as for rendering; the
+ *     results are identical).
+ *   Miss: {t = d_tmax[i] (or 1e20), prim = VRHIP_RAY_MISS, u = 0, v = 0}.
+ *   Non-finite rays (one of the six floats not finite, or a NaN tmax) are
+ *     classified before any traversal and reported as a miss with t = 1e20.
+ *   VRHIP_RAYS_ANY (occlusion): only hit-or-miss is defined and the walk stops
+ *     at the first accepted triangle: {0, 0, 0, 0} when some triangle is hit
+ *     in (3e-10, tmax), the miss record otherwise; hit-or-miss equals the
+ *     closest-hit query's for every ray.
+ * The work runs on the context stream and the call returns when it has
+ * finished.  It touches neither the accumulation, the images, the frame
+ * counter nor the mesh.  n_rays == 0: VRHIP_OK, nothing written.
+ * VRHIP_ERR_INVALID, before any device call, for a null ctx, null origins,
+ * dirs or hits with n_rays > 0, misaligned hits, an unknown mode, no resident
+ * mesh, and a vrhip_create_multi context (the pointers live on one device).
+ * Added without an ABI version change (ABI 6 gained this symbol and
+ * vrhip_flat_trace_rays and changed no other). */
+#define VRHIP_RAY_MISS 0xffffffffu
+typedef struct vrhip_ray_hit { float t; uint32_t prim; float u, v; } vrhip_ray_hit;   /* 16 B */
+enum { VRHIP_RAYS_CLOSEST = 0, VRHIP_RAYS_ANY = 1 };
+int vrhip_trace_rays(vrhip_ctx *ctx, const float *d_origins /*float[3n]*/, const float *d_dirs /*float[3n]*/,
+                     const float *d_tmax /*float[n] or NULL*/, uint32_t n_rays, uint32_t mode,
+                     vrhip_ray_hit *d_hits /*[n]*/);
 /* replaces vRendererCuda::loadHDR (src/vRendererCuda.cpp:320-340) +
  * cu_setHDRDim: rgba float4[w*h] (or half4 with the _half variant, the
  * Imf::Rgba layout, converted on the device). */
@@ -387,7 +435,7 @@ int vrhip_set_overlap(vrhip_ctx *ctx, int mode);
  *   vrhip_gl_present, vrhip_pack_tiles/unpack_tiles, vrhip_last_kernel_ms,
  *   vrhip_kernel_stats, vrhip_debug_counters, vrhip_set_camera, vrhip_clear,
  *   every upload (vrhip_upload_mesh_device too), vrhip_refit_mesh_device,
- *   vrhip_bvh_sah_cost, vrhip_export_mesh_flat, vrhip_set_stream, vrhip_set_tiling, vrhip_set_service
+ *   vrhip_bvh_sah_cost, vrhip_export_mesh_flat, vrhip_trace_rays, vrhip_set_stream, vrhip_set_tiling, vrhip_set_service
  *   (and its timing / budget hooks), vrhip_comm_init/destroy, vrhip_destroy,
  *   the counting renders, and a vrhip_render that does not fit the session.
  *   Calls that do NOT close it: the flag setters (Cornell box, example sphere,
@@ -569,6 +617,17 @@ int vrhip_validate_flat(const float *bvh, size_t n_bvh_f4, const float *verts, s
  * yardstick for the device value, and the cost of a cached tree without a GPU. */
 int vrhip_flat_sah_cost(const float *bvh, size_t n_bvh_f4, const float *verts, size_t n_slots,
                         double *cost);
+/* vrhip_trace_rays on the host over a flattened tree, host pointers throughout
+ * (checked first as vrhip_validate_flat does: VRHIP_ERR_BVH if malformed;
+ * VRHIP_ERR_INVALID for null arrays or an unknown mode): one lane of the
+ * reference's walk (cuda/src/PathTracer.cu:276-463) -- every pierced box, near
+ * child first and child 0 on equal entries, leaf slots in order up to the
+ * terminator, strict < on the closest-hit update.  Same records and semantics;
+ * `prim` is the slot of the hit triangle's first vertex.  The yardstick for the
+ * device query, and ray queries on a cached tree without a GPU. */
+int vrhip_flat_trace_rays(const float *bvh, size_t n_bvh_f4, const float *verts, size_t n_slots,
+                          const float *origins, const float *dirs, const float *tmax, uint32_t n_rays,
+                          uint32_t mode, vrhip_ray_hit *hits);
 
 #ifdef __cplusplus
 }

@@ -75,6 +75,10 @@ struct vrhip_ctx {
     // the refit's validation flags) and the upload's n_verts
     uint32_t* slot_vert = nullptr; uint32_t* node_level = nullptr; vr::DevBuildStatus* refit_status = nullptr;
     uint32_t refit_verts = 0;
+    // what a ray query reports for each compact triangle (uint32[dev_tris]): the
+    // caller's triangle index after a device build, the flat slot of the
+    // triangle's first vertex after a host upload
+    uint32_t* prim_id = nullptr;
     // environment / textures / brdf
     vr4* hdr = nullptr; uint32_t hdr_w = 0, hdr_h = 0;
     vr4* tex[3] = { nullptr, nullptr, nullptr }; uint32_t tex_w[3] = { 0, 0, 0 }, tex_h[3] = { 0, 0, 0 };

@@ -42,12 +42,14 @@ __global__ __launch_bounds__(kBlock) void newpos_kernel(uint32_t n_nodes, const 
 // nothing when a flag is up.
 __global__ __launch_bounds__(kBlock) void emit_tris_kernel(TriSource src, const uint32_t* __restrict__ tris,
                                                            uint32_t n_tris, const uint32_t* __restrict__ refs,
-                                                           uint32_t n_refs, TriArrays out, const DevBuildStatus* st)
+                                                           uint32_t n_refs, TriArrays out,
+                                                           uint32_t* __restrict__ prim_id, const DevBuildStatus* st)
 {
     const uint32_t k = blockIdx.x * kBlock + threadIdx.x;
     if (k >= n_refs || st->flags != 0u) return;
     const uint32_t t = refs[k];
     if (t >= n_tris) return;
+    prim_id[k] = t;
     const uint32_t vi[3] = { tris[3 * (size_t)t], tris[3 * (size_t)t + 1], tris[3 * (size_t)t + 2] };
     gather_triangle<true>(src, out, k, vi);
 }
@@ -86,7 +88,8 @@ hipError_t emit_order(const EmitArgs& a, hipStream_t s)
 hipError_t emit_tris(const EmitArgs& a, hipStream_t s)
 {
     const TriArrays out{ a.out.verts, a.out.tri_e, a.out.normals, a.out.tangents, a.out.uvs, a.out.slot_vert };
-    emit_tris_kernel<<<blocks_for(a.n_refs), kBlock, 0, s>>>(a.src, a.tris, a.n_tris, a.refs, a.n_refs, out, a.status);
+    emit_tris_kernel<<<blocks_for(a.n_refs), kBlock, 0, s>>>(a.src, a.tris, a.n_tris, a.refs, a.n_refs, out,
+                                                             a.out.prim_id, a.status);
     return hipGetLastError();
 }
 

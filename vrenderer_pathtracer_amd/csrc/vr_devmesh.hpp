@@ -68,10 +68,13 @@ struct DevBuildStatus {
 // tpath u64[n_refs], normals / tangents float4[3 n_refs], uvs vr2[3 n_refs];
 // and what a refit needs (vr_refit.hpp): slot_vert u32[3 n_refs], the caller's
 // vertex index behind each compact vertex slot, and node_level u32[nodes], each
-// node's level in the emitted order (the root 0; refit_levels)
+// node's level in the emitted order (the root 0; refit_levels); and what a
+// ray query reports (vr_rayquery.hpp): prim_id u32[n_refs], the caller's
+// triangle of each compact triangle
 struct DevBuildOut {
     vr4* bvh; vr4* bvh16; vr3* verts; vr3* tri_e; unsigned long long* tpath;
     vr4* normals; vr4* tangents; vr2* uvs; uint32_t* slot_vert; uint32_t* node_level;
+    uint32_t* prim_id;
 };
 
 // A leaf child's index word: ~((first << 7) | count) over the compact triangles

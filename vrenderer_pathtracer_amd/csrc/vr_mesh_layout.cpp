@@ -207,6 +207,7 @@ bool to_device_layout(const float* bvh, size_t n_bvh_f4, const vr4* verts, const
                 uint32_t b;
                 std::memcpy(&b, &verts[s].x, 4);
                 if (b == 0x80000000u) break;
+                dm.prim_id.push_back((uint32_t)s);
                 for (int k = 0; k < 3; ++k) {
                     dm.tris.push_back(vr3{ verts[s + k].x, verts[s + k].y, verts[s + k].z });
                     dm.normals.push_back(normals[s + k]);
@@ -230,6 +231,7 @@ bool to_device_layout(const float* bvh, size_t n_bvh_f4, const vr4* verts, const
         dm.normals.push_back(vr4{ 0, 0, 0, 0 });
         dm.tangents = dm.normals;
         dm.uvs.push_back(vr2{ 0, 0 });
+        dm.prim_id.push_back(0u);
     }
     // The Moller-Trumbore edges are the same fp32 subtractions whichever side
     // performs them; precomputed, the triangle test reads v0 and both edges

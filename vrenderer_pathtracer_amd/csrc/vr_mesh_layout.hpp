@@ -24,6 +24,7 @@ struct DeviceMesh {
     std::vector<vr3> tri_e;          // per triangle v0, v1 - v0, v2 - v0 (fp32, the kernel's own subtractions)
     std::vector<unsigned long long> tpath;   // per triangle: leaf path from the root under a leading 1 bit
     std::vector<vr2> uvs;
+    std::vector<uint32_t> prim_id;   // per triangle: the flat slot of its first vertex (what a ray query reports)
 };
 
 // The arrays must have passed validate_flat.  false: refused, with the reason in `why`.

@@ -16,6 +16,7 @@
 #include "vr_exr.hpp"
 #include "vr_merl.hpp"
 #include "vr_mesh_layout.hpp"
+#include "vr_rayquery.hpp"
 #include "vr_refit.hpp"
 
 namespace {
@@ -162,7 +163,7 @@ int vrhip_destroy(vrhip_ctx* c)
     quiesce(c);
     dfree(c->accum); dfree(c->rgba); dfree(c->depth); dfree(c->cam_sxy);
     dfree(c->bvh); dfree(c->bvh16); dfree(c->verts); dfree(c->tri_e); dfree(c->tpath); dfree(c->normals); dfree(c->tangents); dfree(c->uvs);
-    dfree(c->slot_vert); dfree(c->node_level); dfree(c->refit_status);
+    dfree(c->slot_vert); dfree(c->node_level); dfree(c->refit_status); dfree(c->prim_id);
     dfree(c->hdr); dfree(c->tex[0]); dfree(c->tex[1]); dfree(c->tex[2]); dfree(c->brdf);
     for (int i = 0; i < 2; ++i)
         if (c->gl_res[i]) (void)hipGraphicsUnregisterResource(c->gl_res[i]);
@@ -272,6 +273,7 @@ int one_upload_mesh_flat(vrhip_ctx* c, const float* bvh, size_t n_bvh_f4, const 
     if ((rc = upload(c, c->normals, dm.normals.data(), nt * 16))) return rc;
     if ((rc = upload(c, c->tangents, dm.tangents.data(), nt * 16))) return rc;
     if ((rc = upload(c, c->uvs, dm.uvs.data(), nt * 8))) return rc;
+    if ((rc = upload(c, c->prim_id, dm.prim_id.data(), dm.prim_id.size() * sizeof(uint32_t)))) return rc;
     HIP_TRY(hipStreamSynchronize(c->stream));
     // a host upload keeps no index data: nothing to refit (vrhip_refit_mesh_device)
     dfree(c->slot_vert); dfree(c->node_level); dfree(c->refit_status);
@@ -309,7 +311,7 @@ struct DeviceBuild {
     ~DeviceBuild()
     {
         dfree(o.bvh); dfree(o.bvh16); dfree(o.verts); dfree(o.tri_e); dfree(o.tpath);
-        dfree(o.normals); dfree(o.tangents); dfree(o.uvs); dfree(o.slot_vert); dfree(o.node_level); dfree(status);
+        dfree(o.normals); dfree(o.tangents); dfree(o.uvs); dfree(o.slot_vert); dfree(o.node_level); dfree(o.prim_id); dfree(status);
         if (scratch) (void)hipFree(scratch);
     }
 };
@@ -353,6 +355,7 @@ int vrhip_upload_mesh_device_ex(vrhip_ctx* c, const float* d_positions, const fl
     HIP_TRY(hipMalloc((void**)&b.o.uvs, nv * 8));
     HIP_TRY(hipMalloc((void**)&b.o.slot_vert, nv * sizeof(uint32_t)));
     HIP_TRY(hipMalloc((void**)&b.o.node_level, (size_t)sh.nodes * sizeof(uint32_t)));
+    HIP_TRY(hipMalloc((void**)&b.o.prim_id, (size_t)sh.n_refs * sizeof(uint32_t)));
     HIP_TRY(hipMalloc((void**)&b.status, sizeof(vr::DevBuildStatus)));
     HIP_TRY(hipMemsetAsync(b.status, 0, sizeof(vr::DevBuildStatus), c->stream));
     const int e = (sah ? vr::devsah_build : vr::devbvh_build)(d_positions, d_normals, d_tangents, d_uvs, n_verts, d_tris,
@@ -372,10 +375,11 @@ int vrhip_upload_mesh_device_ex(vrhip_ctx* c, const float* d_positions, const fl
         return fail(VRHIP_ERR_BVH, "device BVH build: the tree is not the shape its size gives");
     dfree(c->bvh); dfree(c->bvh16); dfree(c->verts); dfree(c->tri_e); dfree(c->tpath);
     dfree(c->normals); dfree(c->tangents); dfree(c->uvs);
-    dfree(c->slot_vert); dfree(c->node_level); dfree(c->refit_status);
+    dfree(c->slot_vert); dfree(c->node_level); dfree(c->refit_status); dfree(c->prim_id);
     c->bvh = b.o.bvh; c->bvh16 = b.o.bvh16; c->verts = b.o.verts; c->tri_e = b.o.tri_e; c->tpath = b.o.tpath;
     c->normals = b.o.normals; c->tangents = b.o.tangents; c->uvs = b.o.uvs;
     c->slot_vert = b.o.slot_vert; c->node_level = b.o.node_level; c->refit_status = b.status;
+    c->prim_id = b.o.prim_id;
     c->refit_verts = n_verts;
     b.o = vr::DevBuildOut{};
     b.status = nullptr;
@@ -445,6 +449,47 @@ int vrhip_flat_sah_cost(const float* bvh, size_t n_bvh_f4, const float* verts, s
     const int v = vr::validate_flat(bvh, n_bvh_f4, verts, n_slots, nullptr, nullptr);
     if (v != 0) return fail(VRHIP_ERR_BVH, "validation failed (code " + std::to_string(v) + ")");
     *cost = vr::flat_sah_cost(bvh, verts);
+    return VRHIP_OK;
+}
+
+// Ray queries against the resident mesh (vr_rayquery.hip): the path kernels'
+// traversal fed from the caller's ray buffer.  Reads the mesh only; the
+// accumulation, the images and the frame counter stay as they are.
+static_assert(sizeof(vrhip_ray_hit) == 16 && sizeof(vr::RayHit) == 16, "one 16-B record per ray");
+int vrhip_trace_rays(vrhip_ctx* c, const float* d_origins, const float* d_dirs, const float* d_tmax, uint32_t n_rays,
+                     uint32_t mode, vrhip_ray_hit* d_hits)
+{
+    if (!c) return fail(VRHIP_ERR_INVALID, "null ctx");
+    if (mode != VRHIP_RAYS_CLOSEST && mode != VRHIP_RAYS_ANY) return fail(VRHIP_ERR_INVALID, "unknown ray query mode");
+    if (n_rays > 0 && (!d_origins || !d_dirs || !d_hits)) return fail(VRHIP_ERR_INVALID, "null ray or hit array");
+    if (((uintptr_t)d_hits & 15u) != 0u) return fail(VRHIP_ERR_INVALID, "d_hits is not 16-byte aligned");
+    if (!c->group.empty()) return refuse_multi(c, "vrhip_trace_rays");
+    if (!c->mesh || c->dev_nodes == 0 || !c->prim_id) return fail(VRHIP_ERR_INVALID, "no mesh loaded");
+    if (n_rays == 0) return VRHIP_OK;
+    int rc = set_device(c); if (rc) return rc;
+    if ((rc = svc_close(c)) != VRHIP_OK) return rc;
+    vr::RenderParams p;
+    std::memset(&p, 0, sizeof(p));
+    p.bvh = c->bvh; p.bvh16 = c->bvh16; p.tri_e = c->tri_e; p.tpath = c->tpath;
+    p.n_nodes = c->dev_nodes; p.n_tris = c->dev_tris;
+    p.flags = vr::F_MESH | (c->strict ? (uint32_t)vr::F_STRICT : 0u);
+    const vr::RayQuery q{ d_origins, d_dirs, d_tmax, n_rays, mode == VRHIP_RAYS_ANY ? 1u : 0u, c->prim_id,
+                          (vr::RayHit*)d_hits };
+    // stack entries needed: walk depth + 1 (as build_params, vrhip_render.cpp)
+    const int stack = c->bvh_depth <= 15 ? 16 : c->bvh_depth <= 23 ? 24 : c->bvh_depth <= 30 ? 32 : 64;
+    const int e = vr::launch_ray_query(p, q, stack, c->cu_count, c->stream);
+    if (e) return fail(VRHIP_ERR_HIP, std::string("ray query: ") + hipGetErrorString((hipError_t)e));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return svc_verify(c);
+}
+
+int vrhip_flat_trace_rays(const float* bvh, size_t n_bvh_f4, const float* verts, size_t n_slots, const float* origins,
+                          const float* dirs, const float* tmax, uint32_t n_rays, uint32_t mode, vrhip_ray_hit* hits)
+{
+    const int rc = vr::flat_trace_rays(bvh, n_bvh_f4, verts, n_slots, origins, dirs, tmax, n_rays, mode,
+                                       (vr::RayHit*)hits);
+    if (rc == VRHIP_ERR_BVH) return fail(VRHIP_ERR_BVH, "flattened BVH failed validation");
+    if (rc != VRHIP_OK) return fail(VRHIP_ERR_INVALID, "null array or unknown ray query mode");
     return VRHIP_OK;
 }
 

@@ -93,6 +93,50 @@ def flat_sah_cost(flat: dict) -> float:
     return cost.value
 
 
+RAY_MISS = 0xFFFFFFFF                    # VRHIP_RAY_MISS
+RAYS_CLOSEST, RAYS_ANY = 0, 1           # vrhip_trace_rays modes
+
+
+def _unpack_hits(rec, xp):
+    """The (N,4) int32 records of vrhip_ray_hit as the dict the ray queries
+    return: t, u, v float32 and prim int64 with -1 for a miss.  xp: numpy or torch."""
+    prim = rec[:, 1].astype(np.int64) if xp is np else rec[:, 1].to(xp.int64)
+    prim = xp.where(prim < 0, prim + (1 << 32), prim)          # the uint32 behind the int32
+    prim = xp.where(prim == RAY_MISS, xp.full_like(prim, -1), prim)
+    f = rec.view(np.float32) if xp is np else rec.view(xp.float32)
+    if xp is np:
+        return {"t": f[:, 0].copy(), "prim": prim, "u": f[:, 2].copy(), "v": f[:, 3].copy()}
+    return {"t": f[:, 0].contiguous(), "prim": prim, "u": f[:, 2].contiguous(), "v": f[:, 3].contiguous()}
+
+
+def flat_trace_rays(flat: dict, origins, dirs, tmax=None, any_hit: bool = False) -> dict:
+    """Ray queries against a flattened tree on the host (vrhip_flat_trace_rays):
+    one lane of the reference's walk, the yardstick of VRendererHIP.traceRays.
+    origins, dirs (N,3) float32, tmax (N,) float32 or None (1e20).  Returns
+    numpy arrays t, u, v (N,) float32 and prim (N,) int64: the slot of the hit
+    triangle's first vertex in flat["verts"], -1 for a miss.  With any_hit
+    only hit-or-miss is defined (a hit is t = 0, prim = 0).  Raises if the tree
+    is malformed."""
+    L = _native.lib()
+    bvh = _f32(flat["bvh"])
+    verts = _f32(flat["verts"])
+    o = _f32(origins).reshape(-1, 3)
+    d = _f32(dirs).reshape(-1, 3)
+    n = o.shape[0]
+    if d.shape[0] != n:
+        raise ValueError(f"dirs: shape {d.shape} (expected ({n}, 3))")
+    tm = None
+    if tmax is not None:
+        tm = _f32(tmax).reshape(-1)
+        if tm.shape[0] != n:
+            raise ValueError(f"tmax: shape {tm.shape} (expected ({n},))")
+    rec = np.zeros((n, 4), np.int32)
+    check(L.vrhip_flat_trace_rays(fptr(bvh), bvh.size // 4, fptr(verts), verts.size // 4, fptr(o), fptr(d), fptr(tm), n,
+                                  RAYS_ANY if any_hit else RAYS_CLOSEST, ctypes.c_void_p(rec.ctypes.data)),
+          "vrhip_flat_trace_rays")
+    return _unpack_hits(rec, np)
+
+
 _POWF_LUTS = {}
 
 
@@ -309,6 +353,36 @@ class VRendererHIP:
         check(self._lib.vrhip_bvh_sah_cost(self._need_ctx(), ctypes.byref(cost)), "vrhip_bvh_sah_cost")
         return cost.value
 
+    def traceRays(self, origins, dirs, tmax=None, any_hit: bool = False) -> dict:
+        """Where do these rays hit the resident mesh (vrhip_trace_rays)?
+        origins, dirs: (N,3) float32 torch tensors on the renderer's GPU,
+        contiguous; tmax: (N,) float32 or None (1e20).  Directions are used as
+        given (t is in units of their length).  Only the triangle mesh is
+        tested, whatever the scene flags say.  Returns device tensors t, u, v
+        (N,) float32 and prim (N,) int64, -1 for a miss: the triangle's row in
+        initMeshDevice's tris, or, for a mesh from initMesh, the slot of its
+        first vertex in the flattened verts.  With any_hit only hit-or-miss is
+        defined (a hit is t = 0, prim = 0).  ValueError for a wrong device,
+        dtype, shape or layout.  Synchronises torch's current stream first;
+        the query runs on the renderer's own stream and has finished on return."""
+        import torch
+        self._need_ctx()
+        dev = self._torch_device()
+        ptr = self._tensor_ptr
+        p_o = ptr("origins", origins, 3, (torch.float32,))
+        if p_o is None:
+            raise ValueError("origins and dirs are required")
+        n = int(origins.shape[0])
+        p_d = ptr("dirs", dirs, 3, (torch.float32,), n)
+        if p_d is None:
+            raise ValueError("origins and dirs are required")
+        p_t = ptr("tmax", tmax, None, (torch.float32,), n)
+        rec = torch.empty((n, 4), dtype=torch.int32, device=f"cuda:{dev}")
+        torch.cuda.current_stream(dev).synchronize()
+        check(self._lib.vrhip_trace_rays(self._ctx, p_o, p_d, p_t, n, RAYS_ANY if any_hit else RAYS_CLOSEST,
+                                         ctypes.c_void_p(rec.data_ptr())), "vrhip_trace_rays")
+        return _unpack_hits(rec, torch)
+
     def _torch_device(self) -> int:
         """The GPU index device tensors must live on (a group's first device)."""
         if isinstance(self._device, (list, tuple)):
@@ -317,7 +391,8 @@ class VRendererHIP:
 
     def _tensor_ptr(self, name, t, cols, dtypes, rows=None):
         """The device pointer of an (N, cols) torch tensor on the renderer's
-        GPU, or None for None; ValueError for anything else."""
+        GPU (cols None: an (N,) tensor), or None for None; ValueError for
+        anything else."""
         import torch
         dev = self._torch_device()
         if t is None:
@@ -328,7 +403,10 @@ class VRendererHIP:
             raise ValueError(f"{name}: tensor is on {t.device}, the renderer on GPU {dev}")
         if t.dtype not in dtypes:
             raise ValueError(f"{name}: dtype {t.dtype} (expected {' or '.join(str(d) for d in dtypes)})")
-        if t.dim() != 2 or t.shape[1] != cols or (rows is not None and t.shape[0] != rows):
+        if cols is None:
+            if t.dim() != 1 or (rows is not None and t.shape[0] != rows):
+                raise ValueError(f"{name}: shape {tuple(t.shape)} (expected ({'N' if rows is None else rows},))")
+        elif t.dim() != 2 or t.shape[1] != cols or (rows is not None and t.shape[0] != rows):
             raise ValueError(f"{name}: shape {tuple(t.shape)} (expected ({'N' if rows is None else rows}, {cols}))")
         if not t.is_contiguous():
             raise ValueError(f"{name}: tensor is not contiguous")
