@@ -268,6 +268,30 @@ def test_eight_tile_ranks_full_size_reassemble_bitexact(native, cfg):
         assert np.array_equal(g, e), f"{cfg} {what}: {int((g != e).any(-1).sum())} pixels differ"
 
 
+@pytest.mark.parametrize("devices", [[0], [0, 1]])
+def test_multi_context_mesh_reupload_bitexact(native, devices):
+    """initMesh on a multi-device context lays the tree out once and uploads
+    it to every member; a second initMesh replaces every member's mesh.  After
+    each, the group renders what the plain context renders, bit for bit.  (A
+    device cannot appear twice in a group: two members need two GPUs.)"""
+    from vrenderer_pathtracer_amd import VRendererHIP, device_count, scenes
+    if device_count() < len(devices):
+        pytest.skip("needs 2 GPUs (one process drives both)")
+    times = [4242, 4249]
+    r = VRendererHIP(list(devices))
+    scenes.load_into(r, scenes.make_scene("C2", 64, 48, knot=(40, 20)))
+    for knot in ((40, 20), (60, 30), (40, 20)):
+        sc = scenes.make_scene("C2", 64, 48, knot=knot)
+        r.initMesh(sc["mesh_flat"])
+        r.clearBuffer()
+        r.render(frames=2, times=times)
+        ga, gr, gd = r.read_accum(), r.read_rgba8(), r.read_depth8()
+        sa, sr, sd = _single(sc, 2, times)
+        assert np.array_equal(ga.view(np.uint32), sa.view(np.uint32)), knot
+        assert np.array_equal(gr, sr) and np.array_equal(gd, sd), knot
+    r.cleanUp()
+
+
 def test_multi_context_two_devices_bitexact(native):
     """Two GPUs behind one context: each renders half the tiles, RCCL gathers
     them to the first; the images equal the one-GPU render bit for bit."""

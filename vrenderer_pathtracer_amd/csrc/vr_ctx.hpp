@@ -1,7 +1,7 @@
-// vr_ctx.hpp -- internal to the host half of libvrhip.so (vrhip_scene, _service, _render, _multi and
-// _selftest.cpp, which implement include/vrhip.h): the context, the error helpers and the functions
-// one unit calls in another.  The host half is the device-side counterpart of vRendererCuda
-// (src/vRendererCuda.cpp) and the cu_* device ABI (cuda/include/PathTracer.cuh:107-165), re-designed
+// vr_ctx.hpp -- internal to the host half of libvrhip.so (vrhip_scene, _mesh, _service, _render, _multi
+// and _selftest.cpp, which implement include/vrhip.h): the context, the resident mesh it owns, the error
+// helpers and the functions one unit calls in another.  The host half is the device-side counterpart of
+// vRendererCuda (src/vRendererCuda.cpp) and the cu_* device ABI (cuda/include/PathTracer.cuh:107-165), re-designed
 // around one context per GPU, status codes instead of exit(0) (src/vRendererCuda.cpp:454-467), flags
 // passed by value in the launch instead of __constant__ symbol copies (cuda/src/PathTracer.cu:976-1001),
 // and multi-frame render steps.
@@ -12,6 +12,7 @@
 #include <chrono>
 #include <cstdint>
 #include <deque>
+#include <memory>
 #include <string>
 #include <utility>
 #include <vector>
@@ -40,6 +41,80 @@ int fail(int code, const std::string& msg);
 template <typename T>
 void dfree(T*& p) { if (p) { (void)hipFree((void*)p); p = nullptr; } }
 
+// a device temporary that is freed on every way out of its scope
+struct DevFree { void operator()(void* p) const { (void)hipFree(p); } };
+template <typename T>
+using dev_ptr = std::unique_ptr<T, DevFree>;
+template <typename T>
+hipError_t dev_alloc(dev_ptr<T>& p, size_t bytes)
+{
+    void* raw = nullptr;
+    const hipError_t e = hipMalloc(&raw, bytes);
+    p.reset((T*)raw);
+    return e;
+}
+
+// The resident triangle mesh and the one place that frees it: the arrays the
+// kernels, the builders, the refit and the ray query share (vr_devmesh.hpp
+// MeshArrays: pointers, compact nodes and triangles, depth) and what only the
+// host keeps.  An upload fills a fresh one and swaps it with the context's
+// when nothing failed, so a refused mesh leaves the resident one as it was;
+// the old arrays go when the fresh one's scope ends.  A loaded mesh has at
+// least one node.
+struct ResidentMesh {
+    vr::MeshArrays a{};
+    // a device build's status record, reused for the refit's validation flags;
+    // with a.slot_vert and a.node_level what vrhip_refit_mesh_device needs
+    // (all three null after a host upload, which keeps no index data)
+    vr::DevBuildStatus* status = nullptr;
+    size_t n_bvh = 0, n_slots = 0;                // the reference layout's float4 rows and slots
+    uint32_t bvh_nodes = 0;                       // its node count (vrhip_bvh_info)
+    uint32_t refit_verts = 0;                     // the device upload's n_verts
+
+    ResidentMesh() = default;
+    ResidentMesh(const ResidentMesh&) = delete;
+    ResidentMesh& operator=(const ResidentMesh&) = delete;
+    ResidentMesh(ResidentMesh&& o) noexcept { swap(o); }
+    ResidentMesh& operator=(ResidentMesh&& o) noexcept { swap(o); return *this; }
+    ~ResidentMesh()
+    {
+        dfree(a.bvh); dfree(a.bvh16); dfree(a.verts); dfree(a.tri_e); dfree(a.tpath); dfree(a.normals);
+        dfree(a.tangents); dfree(a.uvs); dfree(a.slot_vert); dfree(a.node_level); dfree(a.prim_id); dfree(status);
+    }
+    bool loaded() const { return a.bvh != nullptr; }
+    void swap(ResidentMesh& o)
+    {
+        std::swap(a, o.a); std::swap(status, o.status); std::swap(n_bvh, o.n_bvh); std::swap(n_slots, o.n_slots);
+        std::swap(bvh_nodes, o.bvh_nodes); std::swap(refit_verts, o.refit_verts);
+    }
+    // arrays for max_nodes nodes and n_refs compact triangles (every array at
+    // least 16 bytes) into an empty mesh; with_refit_data: slot_vert,
+    // node_level and the status record too.  The shape fields stay the caller's.
+    int alloc(uint32_t max_nodes, uint32_t n_refs, bool with_refit_data)
+    {
+        auto get = [](auto*& p, size_t bytes) {
+            const hipError_t e = hipMalloc((void**)&p, bytes ? bytes : 16);
+            if (e != hipSuccess) (void)hipGetLastError();    // reported here: later launches check hipGetLastError
+            return e;
+        };
+        const size_t nv = 3 * (size_t)n_refs;
+        HIP_TRY(get(a.bvh, 4 * (size_t)max_nodes * 16));
+        HIP_TRY(get(a.bvh16, 2 * (size_t)max_nodes * 16));
+        HIP_TRY(get(a.verts, nv * sizeof(vr3)));
+        HIP_TRY(get(a.tri_e, nv * sizeof(vr3)));
+        HIP_TRY(get(a.tpath, (size_t)n_refs * sizeof(unsigned long long)));
+        HIP_TRY(get(a.normals, nv * 16));
+        HIP_TRY(get(a.tangents, nv * 16));
+        HIP_TRY(get(a.uvs, nv * 8));
+        HIP_TRY(get(a.prim_id, (size_t)n_refs * sizeof(uint32_t)));
+        if (!with_refit_data) return VRHIP_OK;
+        HIP_TRY(get(a.slot_vert, nv * sizeof(uint32_t)));
+        HIP_TRY(get(a.node_level, (size_t)max_nodes * sizeof(uint32_t)));
+        HIP_TRY(get(status, sizeof(vr::DevBuildStatus)));
+        return VRHIP_OK;
+    }
+};
+
 // Path streams (see render_impl): launch i's kernels wait for the finish
 // pass of launch i - VR_PATH_STREAMS, the last reader of the same scratch.
 #ifndef VR_PATH_STREAMS
@@ -63,22 +138,7 @@ struct vrhip_ctx {
     float fresnel_coef = 0.1f, fresnel_pow = 3.f; // src/vRendererCuda.cpp:27-28
     bool cornell = false, example = false, view_brdf = false;
     bool strict = false;          // exact reference traversal (no t-culling)
-    // mesh
-    vr4* bvh = nullptr; vr4* bvh16 = nullptr; vr3* verts = nullptr; vr3* tri_e = nullptr; unsigned long long* tpath = nullptr; vr4* normals = nullptr; vr4* tangents = nullptr; vr2* uvs = nullptr;
-    size_t n_bvh = 0, n_slots = 0;
-    uint32_t bvh_depth = 0, bvh_nodes = 0, dev_nodes = 0, dev_tris = 0;
-    bool mesh = false;
-    // what a device build leaves for vrhip_refit_mesh_device (null after a host
-    // upload): the caller's vertex index behind each compact vertex slot
-    // (uint32[3 dev_tris]), each node's level in the emitted order
-    // (uint32[dev_nodes], the root 0), the build's status record (reused for
-    // the refit's validation flags) and the upload's n_verts
-    uint32_t* slot_vert = nullptr; uint32_t* node_level = nullptr; vr::DevBuildStatus* refit_status = nullptr;
-    uint32_t refit_verts = 0;
-    // what a ray query reports for each compact triangle (uint32[dev_tris]): the
-    // caller's triangle index after a device build, the flat slot of the
-    // triangle's first vertex after a host upload
-    uint32_t* prim_id = nullptr;
+    ResidentMesh mesh;            // the triangle mesh (vrhip_mesh.cpp)
     // environment / textures / brdf
     vr4* hdr = nullptr; uint32_t hdr_w = 0, hdr_h = 0;
     vr4* tex[3] = { nullptr, nullptr, nullptr }; uint32_t tex_w[3] = { 0, 0, 0 }, tex_h[3] = { 0, 0, 0 };
@@ -273,8 +333,6 @@ int one_use_cornell_box(vrhip_ctx* c, int e);
 int one_use_example_sphere(vrhip_ctx* c, int e);
 int one_set_strict_traversal(vrhip_ctx* c, int e);
 int one_use_brdf(vrhip_ctx* c, int e);
-int one_upload_mesh_flat(vrhip_ctx* c, const float* bvh, size_t n_bvh_f4, const float* verts,
-                         const float* normals, const float* tangents, const float* uvs, size_t n_slots);
 int one_upload_hdr(vrhip_ctx* c, const float* rgba, uint32_t w, uint32_t h);
 int one_upload_hdr_half(vrhip_ctx* c, const uint16_t* rgba_half, uint32_t w, uint32_t h);
 int one_upload_texture(vrhip_ctx* c, int type, const float* rgba, uint32_t w, uint32_t h);
@@ -285,6 +343,19 @@ int multi_gather(vrhip_ctx* c, int what);
 int multi_images(vrhip_ctx* c);
 
 inline int set_device(vrhip_ctx* c) { HIP_TRY(hipSetDevice(c->device)); return VRHIP_OK; }
+
+// The mesh fields of a launch's parameters; all zero when nothing is loaded.
+inline void mesh_params(const ResidentMesh& m, vr::RenderParams& p)
+{
+    const vr::MeshArrays& a = m.a;
+    p.bvh = a.bvh; p.bvh16 = a.bvh16; p.verts = a.verts; p.tri_e = a.tri_e; p.tpath = a.tpath;
+    p.normals = a.normals; p.tangents = a.tangents; p.uvs = a.uvs;
+    p.n_nodes = a.n_nodes; p.n_tris = a.n_refs;
+}
+
+// traversal stack entries for a tree of this depth (the walk needs depth + 1),
+// rounded up to a size the kernels are built for
+inline int mesh_stack_entries(uint32_t depth) { return depth <= 15 ? 16 : depth <= 23 ? 24 : depth <= 30 ? 32 : 64; }
 
 inline uint32_t rendered_rows(const vrhip_ctx* c) { return (c->H / 16u) * 16u; }
 

@@ -210,7 +210,7 @@ struct MortonChildren {
 } // namespace
 
 int devbvh_build(const float* positions, const float* normals, const float* tangents, const float* uvs,
-                 uint32_t n_verts, const uint32_t* tris, uint32_t n_tris, uint32_t max_leaf, const DevBuildOut& out,
+                 uint32_t n_verts, const uint32_t* tris, uint32_t n_tris, uint32_t max_leaf, const MeshArrays& out,
                  DevBuildStatus* d_status, void** scratch_out, void* stream)
 {
     hipStream_t s = (hipStream_t)stream;

@@ -36,6 +36,6 @@ inline DevBuildShape devbvh_shape(uint32_t n_tris, uint32_t max_leaf)
 // a hipError_t; on an error *scratch_out is already freed (null).
 int devbvh_build(const float* positions, const float* normals, const float* tangents, const float* uvs,
                  uint32_t n_verts, const uint32_t* tris, uint32_t n_tris, uint32_t max_leaf,
-                 const DevBuildOut& out, DevBuildStatus* d_status, void** scratch_out, void* stream);
+                 const MeshArrays& out, DevBuildStatus* d_status, void** scratch_out, void* stream);
 
 } // namespace vr

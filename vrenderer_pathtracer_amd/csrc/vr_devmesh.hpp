@@ -1,6 +1,6 @@
 // vr_devmesh.hpp -- what the device builders (vr_devbvh.hip, vr_devsah.hip)
 // and the refit (vr_refit.hip) share about the device mesh layout
-// (vr_mesh_layout.hpp DeviceMesh): the status record, the output arrays, the
+// (vr_mesh_layout.hpp DeviceMesh): the status record, the mesh's arrays, the
 // leaf code, the box and the fp16 rounding of the node rows.  Host-compilable:
 // tests/half_driver.cpp and tests/sah_driver.cpp compile this text.  The
 // device side is vr_devmesh_dev.hpp and vr_devmesh.hip.
@@ -63,18 +63,25 @@ struct DevBuildStatus {
     uint32_t pad[3];
 };
 
-// the eight arrays of the device mesh, allocated by the caller:
-// bvh float4[4 nodes], bvh16 float4[2 nodes], verts / tri_e vr3[3 n_refs],
-// tpath u64[n_refs], normals / tangents float4[3 n_refs], uvs vr2[3 n_refs];
-// and what a refit needs (vr_refit.hpp): slot_vert u32[3 n_refs], the caller's
-// vertex index behind each compact vertex slot, and node_level u32[nodes], each
-// node's level in the emitted order (the root 0; refit_levels); and what a
-// ray query reports (vr_rayquery.hpp): prim_id u32[n_refs], the caller's
-// triangle of each compact triangle
-struct DevBuildOut {
+// The one description of a device mesh's arrays (device pointers; the host's
+// resident mesh owns them, vr_ctx.hpp ResidentMesh).  The eight the path
+// kernels read: bvh float4[4 n_nodes], bvh16 float4[2 n_nodes], verts / tri_e
+// vr3[3 n_refs], tpath u64[n_refs], normals / tangents float4[3 n_refs], uvs
+// vr2[3 n_refs].  What a refit needs (vr_refit.hpp; null after a host upload):
+// slot_vert u32[3 n_refs], the caller's vertex index behind each compact
+// vertex slot, and node_level u32[n_nodes], each node's level in the emitted
+// order (the root 0; refit_levels).  What a ray query reports
+// (vr_rayquery.hpp): prim_id u32[n_refs], the caller's triangle of each
+// compact triangle after a device build, the flat slot of its first vertex
+// after a host upload.
+// The shape: nodes and compact triangles in use, and the tree's depth as
+// DevBuildStatus counts it.  The builders fill arrays sized for their worst
+// case and report the shape through DevBuildStatus: they ignore these three.
+struct MeshArrays {
     vr4* bvh; vr4* bvh16; vr3* verts; vr3* tri_e; unsigned long long* tpath;
     vr4* normals; vr4* tangents; vr2* uvs; uint32_t* slot_vert; uint32_t* node_level;
     uint32_t* prim_id;
+    uint32_t n_nodes, n_refs, depth;
 };
 
 // A leaf child's index word: ~((first << 7) | count) over the compact triangles

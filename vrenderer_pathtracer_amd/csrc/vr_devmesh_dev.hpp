@@ -167,7 +167,7 @@ struct EmitArgs {
     const uint32_t* tris;
     EmitScratch scratch;
     char* temp; size_t temp_bytes;                // for the sort (emit_sort_temp_bytes)
-    DevBuildOut out;
+    MeshArrays out;                               // the pointers only: the shape is what this call reports
     DevBuildStatus* status;
 };
 

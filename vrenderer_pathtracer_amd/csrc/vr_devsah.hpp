@@ -105,6 +105,6 @@ size_t devsah_arena_bytes(uint32_t n_tris);
 // when it returns.  d_status->depth is the tree's real depth.
 int devsah_build(const float* positions, const float* normals, const float* tangents, const float* uvs,
                  uint32_t n_verts, const uint32_t* tris, uint32_t n_tris, uint32_t max_leaf,
-                 const DevBuildOut& out, DevBuildStatus* d_status, void** scratch_out, void* stream);
+                 const MeshArrays& out, DevBuildStatus* d_status, void** scratch_out, void* stream);
 
 } // namespace vr

@@ -179,22 +179,21 @@ int refit_levels(const vr4* bvh, uint32_t n_nodes, uint32_t depth, uint32_t* lev
     return (int)hipGetLastError();
 }
 
-int refit_validate(const float* positions, uint32_t n_verts, const uint32_t* slot_vert, uint32_t n_refs,
-                   DevBuildStatus* st, void* stream)
+int refit_validate(const float* positions, uint32_t n_verts, const MeshArrays& m, DevBuildStatus* st, void* stream)
 {
-    const size_t n_slots = 3 * (size_t)n_refs;
-    refit_validate_kernel<<<blocks_for(n_slots), kBlock, 0, (hipStream_t)stream>>>(positions, n_verts, slot_vert,
+    const size_t n_slots = 3 * (size_t)m.n_refs;
+    refit_validate_kernel<<<blocks_for(n_slots), kBlock, 0, (hipStream_t)stream>>>(positions, n_verts, m.slot_vert,
                                                                                    n_slots, st);
     return (int)hipGetLastError();
 }
 
-int refit_apply(const float* positions, const float* normals, const float* tangents, const RefitMesh& m, void* stream)
+int refit_apply(const float* positions, const float* normals, const float* tangents, const MeshArrays& m, void* stream)
 {
     hipStream_t s = (hipStream_t)stream;
     refit_tris_kernel<<<blocks_for(m.n_refs), kBlock, 0, s>>>(positions, normals, tangents, m.slot_vert, m.n_refs,
                                                               m.verts, m.tri_e, m.normals, m.tangents);
     for (uint32_t d = m.depth; d-- > 0u;)
-        refit_boxes_kernel<<<blocks_for(m.n_nodes), kBlock, 0, s>>>(m.n_nodes, m.n_refs, d, m.level, m.verts,
+        refit_boxes_kernel<<<blocks_for(m.n_nodes), kBlock, 0, s>>>(m.n_nodes, m.n_refs, d, m.node_level, m.verts,
                                                                     (float4*)m.bvh, (uint4*)m.bvh16);
     return (int)hipGetLastError();
 }

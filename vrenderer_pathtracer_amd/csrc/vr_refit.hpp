@@ -19,22 +19,15 @@ namespace vr {
 int refit_levels(const vr4* bvh, uint32_t n_nodes, uint32_t depth, uint32_t* level, void* stream);
 
 // Read-only: ORs DEVBVH_NONFINITE into st->flags when a position behind a
-// compact slot is not finite (DEVBVH_BAD_INDEX when slot_vert itself is out
-// of range).  st must be zero-filled on the stream before the call.
-int refit_validate(const float* positions, uint32_t n_verts, const uint32_t* slot_vert, uint32_t n_refs,
-                   DevBuildStatus* st, void* stream);
+// compact slot of m is not finite (DEVBVH_BAD_INDEX when slot_vert itself is
+// out of range).  st must be zero-filled on the stream before the call.
+int refit_validate(const float* positions, uint32_t n_verts, const MeshArrays& m, DevBuildStatus* st, void* stream);
 
-// The arrays of a resident device mesh, as refit_apply rewrites them.
-struct RefitMesh {
-    vr4* bvh; vr4* bvh16; vr3* verts; vr3* tri_e; vr4* normals; vr4* tangents;
-    const uint32_t* slot_vert; const uint32_t* level;
-    uint32_t n_refs, n_nodes, depth;
-};
-
-// verts, tri_e (and normals / tangents where given) gathered through
-// slot_vert, then every child box of bvh and bvh16, one launch per level,
-// deepest first.  Only after refit_validate found nothing.
-int refit_apply(const float* positions, const float* normals, const float* tangents, const RefitMesh& m,
+// m's verts, tri_e (and normals / tangents where given) gathered through
+// slot_vert, then every child box of bvh and bvh16, one launch per level of
+// node_level, deepest first; tpath, uvs and prim_id stay.  Only after
+// refit_validate found nothing.
+int refit_apply(const float* positions, const float* normals, const float* tangents, const MeshArrays& m,
                 void* stream);
 
 // SAH cost of the tree (1 per node, 1 per triangle) over the root's area, in

@@ -306,9 +306,7 @@ int vrhip_use_cornell_box(vrhip_ctx* c, int e) { return fanout(c, [&](vrhip_ctx*
 int vrhip_use_example_sphere(vrhip_ctx* c, int e) { return fanout(c, [&](vrhip_ctx* m) { return one_use_example_sphere(m, e); }); }
 int vrhip_set_strict_traversal(vrhip_ctx* c, int e) { return fanout(c, [&](vrhip_ctx* m) { return one_set_strict_traversal(m, e); }); }
 int vrhip_use_brdf(vrhip_ctx* c, int e) { return fanout(c, [&](vrhip_ctx* m) { return one_use_brdf(m, e); }); }
-int vrhip_upload_mesh_flat(vrhip_ctx* c, const float* bvh, size_t n_bvh_f4, const float* verts, const float* normals,
-                           const float* tangents, const float* uvs, size_t n_slots)
-{ return fanout(c, [&](vrhip_ctx* m) { return one_upload_mesh_flat(m, bvh, n_bvh_f4, verts, normals, tangents, uvs, n_slots); }); }
+// (vrhip_upload_mesh_flat prepares the arrays once, then fans out itself: vrhip_mesh.cpp)
 int vrhip_upload_hdr(vrhip_ctx* c, const float* rgba, uint32_t w, uint32_t h)
 { return fanout(c, [&](vrhip_ctx* m) { return one_upload_hdr(m, rgba, w, h); }); }
 int vrhip_upload_hdr_half(vrhip_ctx* c, const uint16_t* rgba_half, uint32_t w, uint32_t h)

@@ -287,7 +287,7 @@ static void build_params(const vrhip_ctx* c, RenderCall& q)
     if (c->strict) f |= vr::F_STRICT;
     // the reference skips the mesh while the example sphere is on
     // (PathTracer.cu:192,268): a sphere scene, whatever mesh is loaded
-    if (c->mesh && !c->example) f |= vr::F_MESH;
+    if (c->mesh.loaded() && !c->example) f |= vr::F_MESH;
     if (c->brdf) f |= vr::F_BRDF;
     if (c->tex[0]) f |= vr::F_TEX_DIFF;
     if (c->tex[1]) f |= vr::F_TEX_NORM;
@@ -295,14 +295,13 @@ static void build_params(const vrhip_ctx* c, RenderCall& q)
     p.flags = f;
     p.tiles_x = p.wr / 16u;
     p.rank = c->rank; p.nranks = c->nranks;
-    p.bvh = c->bvh; p.bvh16 = c->bvh16; p.n_nodes = c->mesh ? c->dev_nodes : 0; p.verts = c->verts; p.tri_e = c->tri_e; p.tpath = c->tpath; p.n_tris = c->mesh ? c->dev_tris : 0; p.normals = c->normals; p.tangents = c->tangents; p.uvs = c->uvs;
+    mesh_params(c->mesh, p);
     p.hdr = c->hdr; p.hdr_w = c->hdr_w; p.hdr_h = c->hdr_h;
     for (int i = 0; i < 3; ++i) { p.tex[i] = c->tex[i]; p.tex_w[i] = c->tex_w[i]; p.tex_h[i] = c->tex_h[i]; }
     p.brdf = c->brdf;
     p.accum = c->accum; p.rgba = c->rgba; p.depth = c->depth;
     q.n_tiles = owned_tiles_of(c->W, c->H, c->rank, c->nranks);
-    // stack entries needed: walk depth + 1
-    q.stack = c->bvh_depth <= 15 ? 16 : c->bvh_depth <= 23 ? 24 : c->bvh_depth <= 30 ? 32 : 64;
+    q.stack = mesh_stack_entries(c->mesh.a.depth);
     q.wave_kernel = (f & vr::F_MESH) != 0u;
 }
 
