@@ -212,8 +212,14 @@ int vrhip_refit_mesh_device(vrhip_ctx *ctx, const float *d_positions, const floa
  * area = dx*dy + dy*dz + dz*dx in fp64 from the fp32 boxes, a node's own box
  * the union of its two child boxes, the root included in the first sum.
  * Computed on the device in a fixed order (per-block partials, then one
- * block): two calls return the same bits.  +infinity (and VRHIP_OK) when the
- * root's area is 0 or not finite.  VRHIP_ERR_INVALID with no mesh loaded.
+ * block): two calls return the same bits.  Both this call and
+ * vrhip_flat_sah_cost carry the sum as a pair of doubles with error-free
+ * additions (error below 2^-100 of the sum), although the two visit the nodes
+ * in different orders: in practice the device's value is the host's on the
+ * exported tree bit for bit, and the tests assert that; it is no guarantee,
+ * since a sum within 2^-100 of a rounding boundary of fp64 could still round
+ * either way.  +infinity (and
+ * VRHIP_OK) when the root's area is 0 or not finite.  VRHIP_ERR_INVALID with no mesh loaded.
  * Synchronous. */
 int vrhip_bvh_sah_cost(vrhip_ctx *ctx, double *cost);
 /* The resident mesh, whichever upload call brought it, rewritten on the host
@@ -252,6 +258,19 @@ int vrhip_export_mesh_flat(vrhip_ctx *ctx, float *bvh, size_t *n_bvh_f4, float *
  *     (vrhip_set_strict_traversal selects the walk as for rendering; the
  *     results are identical).
  *   Miss: {t = d_tmax[i] (or 1e20), prim = VRHIP_RAY_MISS, u = 0, v = 0}.
+ *   Every finite ray is answered, whatever its magnitudes, and as the
+ *     reference's walk answers it: where its slab arithmetic overflows or
+ *     cancels, that walk misses triangles a test of every triangle would
+ *     accept, and so does this call.  The fp16 traversal mode is used only
+ *     where it is known to return the reference walk's record: origin and
+ *     mesh coordinates within 8 times the mesh's largest extent, no mesh
+ *     coordinate beyond 65504, no non-zero direction component within 3e-10;
+ *     every other ray is walked strictly in either mode.  Inside that range
+ *     the equality of the two modes is what the tests pin, not a proof: a ray
+ *     that grazes a node box within the last ulp may differ.  A finite ray
+ *     whose arithmetic overflows may return a hit whose u or v is a NaN of
+ *     unspecified sign and payload (the reference's `u < 0 || u > 1` lets a
+ *     NaN through while dist stays finite).  t of a hit is never a NaN.
  *   Non-finite rays (one of the six floats not finite, or a NaN tmax) are
  *     classified before any traversal and reported as a miss with t = 1e20.
  *   VRHIP_RAYS_ANY (occlusion): only hit-or-miss is defined and the walk stops

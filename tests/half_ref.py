@@ -21,6 +21,8 @@ def half_values():
     v = [0.0, -0.0, sub, 3 * sub, 1023 * sub, 1023.5 * sub, sub / 2, sub / 3, 1e-10, 1e-30, 1e-45,
          65504.0, 65505.0, 65519.9, 65520.0, 1e6, 3e38]
     v += [2.0 ** e for e in range(-26, 18)]
+    # the magnitudes of tests/extreme_cases.py: the first float past the largest half, the `huge` mesh, the largest float
+    v += [np.nextafter(np.float32(65504.0), np.float32(np.inf)), 1e37, 3.4e38, np.finfo(np.float32).max]
     v = np.array(v, np.float32)
     bits = rng.integers(0, 0x7F800000, 10000, dtype=np.uint32)            # finite, then both signs
     bits |= rng.integers(0, 2, 10000, dtype=np.uint32) << np.uint32(31)

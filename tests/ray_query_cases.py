@@ -148,25 +148,70 @@ def ray_set(V, n, seed=SEED):
 
 
 # ---- an independent ordering: depth first, near child first ----------------------------
+def _bits(x):
+    return int(np.float32(x).view(np.int32))
+
+
+def _float(i):
+    return np.int32(i).view(np.float32)
+
+
+def _fmin(a, b):
+    """fminf as the reference's GPU evaluates it: a NaN operand is ignored, -0 < +0."""
+    if a != a:
+        return b
+    if b != b:
+        return a
+    if a < b or b < a:
+        return a if a < b else b
+    return a if np.signbit(a) else b
+
+
+def _fmax(a, b):
+    if a != a:
+        return b
+    if b != b:
+        return a
+    if a > b or b > a:
+        return a if a > b else b
+    return b if np.signbit(a) else a
+
+
+# The NaN of an invalid operation (inf - inf): the device makes it with the
+# sign bit set (test_gpu_extreme.py pins that), as x86 and numpy on it do;
+# other hosts clear it, and the integer comparisons below read that bit.  The
+# span is the device's on any host.
+DEVICE_NAN = np.uint32(0xFFC00000).view(np.float32)
+
+
 def _span(n, ch, o, inv):
     """(entry, exit) of the ray's line in child ch's box of node rows n (4,4),
-    clamped to [0, 1e20], in the reference's float32 slab arithmetic."""
+    clamped to [0, 1e20]: spanBeginKepler / spanEndKepler
+    (MathHelpers.cuh:454-552) on the reference's float32 slab arithmetic: a
+    float min / max per axis for x and y, then an integer max / min over the
+    bit patterns, into which z and the clamp enter as integers only."""
     if ch == 0:
         b = [(n[0, 0], n[0, 1]), (n[0, 2], n[0, 3]), (n[2, 0], n[2, 1])]
     else:
         b = [(n[1, 0], n[1, 1]), (n[1, 2], n[1, 3]), (n[2, 2], n[2, 3])]
-    lo, hi = F(0.0), NO_HIT
+    t = []
     for a in range(3):
         od = F(o[a] * inv[a])
-        t0, t1 = F(F(b[a][0] * inv[a]) - od), F(F(b[a][1] * inv[a]) - od)
-        lo, hi = max(lo, min(t0, t1)), min(hi, max(t0, t1))
+        pair = [F(F(b[a][0] * inv[a]) - od), F(F(b[a][1] * inv[a]) - od)]
+        t.append([DEVICE_NAN if x != x else x for x in pair])
+    (x0, x1), (y0, y1), (z0, z1) = t
+    zb = max(min(_bits(z0), _bits(z1)), _bits(F(0.0)))
+    ze = min(max(_bits(z0), _bits(z1)), _bits(NO_HIT))
+    lo = _float(max(_bits(_fmin(x0, x1)), _bits(_fmin(y0, y1)), zb))
+    hi = _float(min(_bits(_fmax(x0, x1)), _bits(_fmax(y0, y1)), ze))
     return lo, hi
 
 
 def dfs_slots(flat, o, d):
     """The triangle slots in the order a depth-first walk of the flat tree
     tests them for this ray: only boxes the ray's line pierces, the nearer
-    child first, child 0 on equal entries, leaf slots in order."""
+    child first, child 0 on equal entries, leaf slots in order.  The spans
+    are the reference's (_span), NaN and signed zeros included."""
     bvh = np.asarray(flat["bvh"], np.float32).reshape(-1, 4, 4)
     vx = u32(flat["verts"][:, 0])
     o, d = np.asarray(o, np.float32), np.asarray(d, np.float32)

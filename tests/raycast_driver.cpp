@@ -1,6 +1,7 @@
 // Stand-alone driver of the host ray query (vr_raycast.cpp) for a sanitizer
 // build (tests/test_ray_query_sanitize.py): rays through a built tree, through
-// a chain tree 40 levels deep and at malformed trees, which must be refused
+// a chain tree 40 levels deep, through trees over meshes at the extremes of
+// float with rays of every magnitude, and at malformed trees, which must be refused
 // with VRHIP_ERR_BVH (-4).  Prints "raycast ok=<accepted> rejected=<refused>"
 // and exits non-zero when a tree lands on the wrong side.
 #include <cmath>
@@ -25,14 +26,18 @@ float bits_to_float(int32_t i) { float f; std::memcpy(&f, &i, 4); return f; }
 
 struct Flat { std::vector<float> bvh, verts; };       // float4 rows
 
-Flat built_tree(uint32_t n_tris, uint32_t max_leaf)
+// scale > 0: every coordinate times scale, clipped to +-3.4e38 (1e37: the
+// extent and the centroids overflow).  scale == 0: each triangle by its own
+// 10^U(-30, 30), a tree next to the builder's depth cap.
+Flat built_tree(uint32_t n_tris, uint32_t max_leaf, double scale = 1.0)
 {
     std::vector<float> pos;
     std::vector<uint32_t> tris;
     for (uint32_t t = 0; t < n_tris; ++t) {
         const float c[3] = { rnd(-30, 30), rnd(-30, 30), rnd(-30, 30) };
+        const double s = scale > 0.0 ? scale : std::pow(10.0, (double)rnd(-30, 30));
         for (int v = 0; v < 3; ++v)
-            for (int a = 0; a < 3; ++a) pos.push_back(c[a] + rnd(-4, 4));
+            for (int a = 0; a < 3; ++a) pos.push_back((float)std::fmax(-3.4e38, std::fmin(3.4e38, s * (double)(c[a] + rnd(-4, 4)))));
         for (uint32_t v = 0; v < 3; ++v) tris.push_back(3 * t + v);
     }
     vr::FlatMesh m;
@@ -76,21 +81,29 @@ Flat chain_tree(int levels)
     return f;
 }
 
-// rays aimed at triangles, random rays, axis-aligned and non-finite ones; both modes, with and without tmax
-int trace(const Flat& f, uint32_t n_rays, uint32_t* hits_out)
+// rays aimed at triangles, random rays, axis-aligned and non-finite ones; both modes, with and without tmax.
+// extreme: origin and direction magnitudes drawn from the whole range of float (1e-45 .. 3e38), zero and
+// -0 directions among them, and tmax from {1e20, inf, 0, -1, 1e-30, 3e38, 1, -inf}
+int trace(const Flat& f, uint32_t n_rays, uint32_t* hits_out, bool extreme = false)
 {
     const size_t n_slots = f.verts.size() / 4;
     std::vector<float> o(3 * (size_t)n_rays), d(3 * (size_t)n_rays), tmax(n_rays);
+    const float ladder[9] = { 1e-45f, 1e-38f, 1e-30f, 1e-10f, 1.f, 1e10f, 1e19f, 1e30f, 3e38f };
+    const float bounds[8] = { 1e20f, INFINITY, 0.f, -1.f, 1e-30f, 3e38f, 1.f, -INFINITY };
     for (uint32_t i = 0; i < n_rays; ++i) {
         const float* v = &f.verts[4 * (size_t)(g_seed % (n_slots ? n_slots : 1))];
+        const float om = extreme ? ladder[(g_seed >> 9) % 9u] : 80.f, dm = extreme ? ladder[(g_seed >> 17) % 9u] : 1.f;
         for (int a = 0; a < 3; ++a) {
-            o[3 * i + a] = rnd(-80, 80);
-            d[3 * i + a] = i % 3 == 0 ? v[a] - o[3 * i + a] : i % 3 == 1 ? rnd(-1, 1) : 0.f;
+            o[3 * i + a] = rnd(-om, om);
+            d[3 * i + a] = i % 3 == 0 ? (extreme ? dm * rnd(0.5f, 1.f) * (v[a] < o[3 * i + a] ? -1.f : 1.f) : v[a] - o[3 * i + a])
+                           : i % 3 == 1 ? rnd(-dm, dm) : (i % 2 ? -0.f : 0.f);
         }
-        if (i % 3 == 2) d[3 * i + i % 3] = 1.f;
-        if (i % 17 == 0) o[3 * i] = NAN;
-        if (i % 19 == 0) d[3 * i + 1] = INFINITY;
-        tmax[i] = i % 23 == 0 ? NAN : rnd(0.1f, 3.f);
+        if (i % 3 == 2 && i % 5 != 0) d[3 * i + i % 3] = dm;    // every fifth of these keeps its all-zero direction
+        if (!extreme) {
+            if (i % 17 == 0) o[3 * i] = NAN;
+            if (i % 19 == 0) d[3 * i + 1] = INFINITY;
+        }
+        tmax[i] = extreme ? bounds[i % 8u] : i % 23 == 0 ? NAN : rnd(0.1f, 3.f);
     }
     std::vector<vr::RayHit> hits(n_rays);
     uint32_t n_hit = 0;
@@ -110,9 +123,9 @@ int trace(const Flat& f, uint32_t n_rays, uint32_t* hits_out)
 int main()
 {
     int ok = 0, rejected = 0, wrong = 0;
-    auto expect = [&](const Flat& f, bool valid, const char* what, bool need_hits = true) {
+    auto expect = [&](const Flat& f, bool valid, const char* what, bool need_hits = true, bool extreme = false) {
         uint32_t n_hit = 0;
-        const int rc = trace(f, 600, &n_hit);
+        const int rc = trace(f, 600, &n_hit, extreme);
         if (rc == 0) ++ok; else ++rejected;
         if (valid ? (rc != 0 || (need_hits && n_hit == 0)) : rc != -4) {
             std::fprintf(stderr, "%s: rc %d, %u hits\n", what, rc, n_hit);
@@ -124,6 +137,11 @@ int main()
     expect(built_tree(65, 3), true, "built tree, leaves of 3");
     expect(one, true, "one triangle", false);       // rays aimed at its corners may graze it
     expect(chain, true, "chain tree");
+    // the extremes of float: no hit is required, only that every operation is defined
+    expect(built, true, "built tree, extreme rays", false, true);
+    expect(built_tree(200, 2, 1e37), true, "huge mesh, extreme rays", false, true);
+    expect(built_tree(200, 1, 0.0), true, "wide mesh, extreme rays", false, true);
+    expect(built_tree(200, 3, 1e18), true, "big mesh, extreme rays", false, true);
 
     Flat bad = built;                                  // a child offset out of range
     bad.bvh[13] = bits_to_float((int32_t)(bad.bvh.size() / 4 + 4));

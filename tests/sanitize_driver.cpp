@@ -122,6 +122,24 @@ int run_bvh()
             for (size_t i = 0; i < h.pos.size(); ++i) h.pos[i] = bad;
             tally(build(h, (uint32_t)(h.pos.size() / 3), leaf, f));
         }
+        // the extremes of float, every value finite: `huge` (x 1e37, clipped to +-3.4e38: the extent and
+        // the centroids overflow, the bin of an infinite centroid is a NaN) must build and validate;
+        // `wide` (each triangle x 10^U(-30, 30): a tree at the depth cap) builds or is refused
+        Mesh huge = random_mesh(200, 37);
+        for (float& x : huge.pos) x = (float)std::fmax(-3.4e38, std::fmin(3.4e38, 1e37 * (double)x));
+        if (build(huge, (uint32_t)(huge.pos.size() / 3), leaf, f) != 0 ||
+            vr::validate_flat(&f.bvh[0].x, f.bvh.size(), &f.verts[0].x, f.verts.size(), &d, &n) != 0) {
+            std::fprintf(stderr, "the huge mesh did not build\n");
+            return 2;
+        }
+        ++ok;
+        Mesh wide = random_mesh(200, 41);
+        Lcg ws(43);
+        for (size_t t = 0; t < wide.pos.size() / 9; ++t) {
+            const double s = std::pow(10.0, 60.0 * (double)ws.unit() - 30.0);
+            for (size_t i = 9 * t; i < 9 * t + 9; ++i) wide.pos[i] = (float)(s * (double)wide.pos[i]);
+        }
+        tally(build(wide, (uint32_t)(wide.pos.size() / 3), leaf, f));
         Mesh oob = random_mesh(10, 19);                                         // index out of range: rejected
         oob.tris[7] = 1000000;
         if (build(oob, (uint32_t)(oob.pos.size() / 3), leaf, f) == 0) { std::fprintf(stderr, "bad index accepted\n"); return 2; }

@@ -11,6 +11,7 @@ import subprocess
 import numpy as np
 import pytest
 
+from extreme_cases import EXTREME_KINDS, extreme_mesh
 from vrenderer_pathtracer_amd import LIB_PATH, _native, build, build_flat, scenes, validate_flat
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -36,7 +37,9 @@ def fnv1a_words(a):
 
 CASES = ([("soup%d" % n, lambda n=n: soup(n), leaf) for n in (2, 3, 5, 63, 64, 65, 257, 1000) for leaf in (1, 2, 4)]
          + [("knot40x20", lambda: scenes.torus_knot(40, 20), 2), ("knot100x50", lambda: scenes.torus_knot(100, 50), 2),
-            ("knot40x20", lambda: scenes.torus_knot(40, 20), 4), ("knot100x50", lambda: scenes.torus_knot(100, 50), 4)])
+            ("knot40x20", lambda: scenes.torus_knot(40, 20), 4), ("knot100x50", lambda: scenes.torus_knot(100, 50), 4)]
+         # the extremes of float: an overflowed extent and centroid (sah_bin's NaN), the depth cap, denormals
+         + [(kind, lambda kind=kind: extreme_mesh(kind), leaf) for kind in EXTREME_KINDS for leaf in (1, 3)])
 
 
 @pytest.fixture(scope="module")

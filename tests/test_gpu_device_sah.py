@@ -8,14 +8,13 @@ import pytest
 
 import device_mesh_cases as cases
 import pyoracle as po
-from device_mesh_cases import HARD_KINDS, bitexact, expected_triangles, hard_mesh, sorted_rows, soup
+from device_mesh_cases import HARD_KINDS, bitexact, expected_triangles, hard_mesh, soup
+from extreme_cases import check_boxes_and_leaves, slot_rows
 from vrenderer_pathtracer_amd import VRendererHIP, VRHIPError, build_flat, scenes, validate_flat
 
 pytestmark = pytest.mark.gpu
 
-TERM = 0x80000000
 T = 64                                                 # kSahSmall (csrc/vr_devsah.hpp): one wave64 per node up to here
-MAX_BUILD_DEPTH = 30                                   # kMaxBuildDepth
 
 
 # ---- builds: this file's default builder is the SAH one ---------------------------
@@ -42,83 +41,22 @@ def host_flat(key, mesh, max_leaf):
 
 
 # ---- the exported tree ---------------------------------------------------------
-def slot_rows(flat):
-    """(is_term, rows): per non-terminator slot triple, the row expected_triangles gives."""
-    verts = flat["verts"]
-    is_term = verts[:, 0].copy().view(np.uint32) == TERM
-    keep = ~is_term
-    assert (verts[keep, 3] == 0).all()
-    rows = np.concatenate([verts[keep, :3], flat["normals"][keep, :3], flat["tangents"][keep, :3], flat["uvs"][keep]], -1)
-    return is_term, np.ascontiguousarray(rows.reshape(-1, 33))
-
-
 def leaf_of_triple(is_term):
     """Per slot triple, the index of its leaf run (runs end at terminators)."""
     run = np.cumsum(is_term) - is_term                 # per slot: terminators before it
     return run[~is_term][::3]
 
 
-def check_boxes_and_leaves(flat, mesh, max_leaf):
-    """A valid tree with exact boxes (bottom-up, as test_gpu_device_build.analyse),
-    every input triangle once, leaves within max_leaf unless at the depth cap."""
-    n_tris = len(mesh["tris"])
-    n_refs = max(n_tris, 2)
-    depth, n_nodes = validate_flat(flat)
-    assert depth <= MAX_BUILD_DEPTH
-    nodes = flat["bvh"].reshape(-1, 4, 4)
-    assert len(nodes) == n_nodes
-    child = nodes[:, 3, :2].copy().view(np.int32)
-    verts = flat["verts"]
-    is_term, rows = slot_rows(flat)
-    term_pos = np.flatnonzero(is_term)
-    L = n_nodes + 1
-    starts = np.sort(~child[child < 0])
-    assert len(starts) == L and len(np.unique(starts)) == L
-    ends = term_pos[np.searchsorted(term_pos, starts)]
-    counts = (ends - starts) // 3
-    assert ((ends - starts) % 3 == 0).all() and counts.min() >= 1
-    if depth < MAX_BUILD_DEPTH:
-        assert counts.max() <= max_leaf, counts.max()
-    assert starts[0] == 0 and (starts[1:] == ends[:-1] + 1).all() and ends[-1] == len(verts) - 1
-    assert len(verts) == 3 * n_refs + L
-    want = expected_triangles(mesh)                    # one triangle is stored twice: two rows
-    assert np.array_equal(sorted_rows(rows), sorted_rows(want))
-    lo_src = np.where(is_term[:, None], np.inf, verts[:, :3]).astype(np.float32)
-    hi_src = np.where(is_term[:, None], -np.inf, verts[:, :3]).astype(np.float32)
-    leaf_lo = np.minimum.reduceat(lo_src, starts, axis=0)
-    leaf_hi = np.maximum.reduceat(hi_src, starts, axis=0)
-    levels, cur = [], np.array([0])
-    while len(cur):
-        levels.append(cur)
-        c = child[cur]
-        cur = c[c >= 0] // 4
-    assert len(levels) == depth
-    own_lo = np.zeros((n_nodes, 3), np.float32)
-    own_hi = np.zeros((n_nodes, 3), np.float32)
-    for lev in reversed(levels):
-        los, his = [], []
-        for ch in range(2):
-            c = child[lev, ch]
-            leaf = c < 0
-            li = np.searchsorted(starts, np.where(leaf, ~c, 0))
-            ni = np.where(leaf, 0, c // 4)
-            lo = np.where(leaf[:, None], leaf_lo[li], own_lo[ni])
-            hi = np.where(leaf[:, None], leaf_hi[li], own_hi[ni])
-            n = nodes[lev]
-            stored_lo = np.stack([n[:, ch, 0], n[:, ch, 2], n[:, 2, 2 * ch]], -1)
-            stored_hi = np.stack([n[:, ch, 1], n[:, ch, 3], n[:, 2, 2 * ch + 1]], -1)
-            assert np.array_equal(stored_lo, lo) and np.array_equal(stored_hi, hi)
-            los.append(lo)
-            his.append(hi)
-        own_lo[lev] = np.minimum(los[0], los[1])
-        own_hi[lev] = np.maximum(his[0], his[1])
-    return depth, n_nodes
-
-
-def check_is_host_tree(flat, info, host, mesh):
-    """The issue's equalities between a device SAH export and vrhip_build_flat's tree."""
+def check_is_host_tree(flat, info, host, mesh, zero_sign_free=False):
+    """The issue's equalities between a device SAH export and vrhip_build_flat's tree.
+    zero_sign_free: a box value that is zero may differ in its sign (vrhip.h's one exception)."""
     assert flat["bvh"].shape == host["bvh"].shape
-    assert flat["bvh"].tobytes() == host["bvh"].tobytes()
+    if zero_sign_free:
+        rows = lambda f: f["bvh"].reshape(-1, 4, 4)                      # noqa: E731
+        assert rows(flat)[:, 3].tobytes() == rows(host)[:, 3].tobytes()
+        assert (rows(flat)[:, :3] + np.float32(0.0)).tobytes() == (rows(host)[:, :3] + np.float32(0.0)).tobytes()
+    else:
+        assert flat["bvh"].tobytes() == host["bvh"].tobytes()
     depth, n_nodes = validate_flat(flat)
     assert (depth, n_nodes) == validate_flat(host)
     assert info == (depth, n_nodes, len(flat["verts"]))

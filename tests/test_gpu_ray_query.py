@@ -20,7 +20,8 @@ pytestmark = pytest.mark.gpu
 N_RAYS = 1000
 UPLOADS = BUILDERS + ["host"]
 MESHES = {f"soup{n}-leaf{leaf}": ((lambda n=n: soup(n)), leaf) for n in (1, 2, 65, 1000) for leaf in (1, 3)}
-MESHES.update({kind: ((lambda kind=kind: hard_mesh(kind)), 2) for kind in ("identical", "shared", "zero_area", "flat_axis")})
+MESHES.update({kind: ((lambda kind=kind: hard_mesh(kind)), 2) for kind in ("identical", "shared", "zero_area", "flat_axis",
+                                                                             "far", "equal_centres", "no_attributes")})
 FIELDS = ("t", "u", "v")
 
 

@@ -9,7 +9,7 @@ import pytest
 
 import pyoracle as po
 from device_mesh_cases import BUILDERS, bitexact, deform, device_build, fresh, loaded, soup
-from test_gpu_device_sah import check_boxes_and_leaves
+from extreme_cases import check_boxes_and_leaves
 from vrenderer_pathtracer_amd import VRendererHIP, VRHIPError, flat_sah_cost, scenes, validate_flat
 
 pytestmark = pytest.mark.gpu

@@ -7,10 +7,11 @@ src/BRDFLoader.cpp:15-50), the BVH builder and the flattened-tree validator
 src/vRendererCuda.cpp:204-279 and uploads in :282-317), and the conversion of
 a flattened tree to the device mesh layout and back (vr_mesh_layout.cpp).
 
-tests/sanitize_driver.cpp is compiled with g++ -fsanitize=address,undefined
--fno-sanitize-recover=all together with those sources (no HIP) and fed valid
+tests/sanitize_driver.cpp is compiled with g++
+-fsanitize=address,undefined,float-cast-overflow (GCC's `undefined` leaves
+float-cast-overflow out) -fno-sanitize-recover=all together with those sources (no HIP) and fed valid
 files, every truncation of them, byte-flipped copies, hostile headers,
-degenerate meshes and corrupted flat arrays.  Every input must be accepted or
+degenerate meshes, meshes at the extremes of float and corrupted flat arrays.  Every input must be accepted or
 rejected with an error -- no sanitizer report, no crash."""
 import os
 import shutil
@@ -34,7 +35,7 @@ def driver(tmp_path_factory):
     if not gxx:
         pytest.skip("g++ not available")
     out = str(tmp_path_factory.mktemp("san") / "sanitize_driver")
-    cmd = [gxx, "-std=c++17", "-O1", "-g", "-fno-omit-frame-pointer", "-fsanitize=address,undefined",
+    cmd = [gxx, "-std=c++17", "-O1", "-g", "-fno-omit-frame-pointer", "-fsanitize=address,undefined,float-cast-overflow",
            "-fno-sanitize-recover=all", "-pthread", "-I", CSRC, os.path.join(REPO, "tests", "sanitize_driver.cpp"),
            os.path.join(CSRC, "vr_bvh.cpp"), os.path.join(CSRC, "vr_exr.cpp"), os.path.join(CSRC, "vr_merl.cpp"),
            os.path.join(CSRC, "vr_mesh_layout.cpp"), "-lz", "-o", out]
@@ -159,8 +160,11 @@ def test_merl_reader_under_sanitizers(driver, tmp_path):
 
 
 def test_bvh_builder_under_sanitizers(driver):
+    """Per max_leaf in (0, 1, 2, 8): 18 degenerate or hostile meshes, a `huge`
+    and a `wide` one at the extremes of float (tests/extreme_cases.py has their
+    recipes) and 2 refusals (an index out of range, no triangles)."""
     ok, rejected = _run(driver, "bvh")
-    assert ok >= 4 and rejected >= 8, (ok, rejected)
+    assert ok == 4 * 20 and rejected == 4 * 2, (ok, rejected)
 
 
 def test_flat_validator_under_sanitizers(driver):

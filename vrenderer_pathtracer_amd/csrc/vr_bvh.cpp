@@ -13,6 +13,7 @@
 //   idx >= 0: float4 offset of an inner child; idx < 0: ~first slot of a leaf
 //   leaf run: 3 slots per triangle, then one terminator slot (x bits 0x80000000).
 #include "vr_bvh.hpp"
+#include "vr_devmesh.hpp"
 
 #include <algorithm>
 #include <atomic>
@@ -99,6 +100,14 @@ struct Builder {
         Box box[3][kBins];
         uint32_t cnt[3][kBins] = {};
     };
+    // The bin of a scaled centroid offset.  A centroid 0.5f * (lo + hi) that
+    // overflowed to infinity meets scale = kBins / inf = 0 and gives NaN, which
+    // no cast to int defines: it is bin 0 (tests/test_extreme_cpu.py, and
+    // sah_bin in vr_devsah.hpp is the device's twin).
+    static int bin_of(double x) {
+        const int k = x == x ? (int)x : 0;
+        return std::min(std::max(k, 0), kBins - 1);
+    }
     void bin(uint32_t first, uint32_t count, const Box& cb, Bins& out) const {
         for (int a = 0; a < 3; ++a) {
             const float ext = cb.hi[a] - cb.lo[a];
@@ -106,8 +115,7 @@ struct Builder {
             const double scale = kBins / (double)ext;
             for (uint32_t i = first; i < first + count; ++i) {
                 const uint32_t t = refs[i];
-                int k = (int)(((double)centroid[3 * t + a] - cb.lo[a]) * scale);
-                k = std::min(std::max(k, 0), kBins - 1);
+                const int k = bin_of(((double)centroid[3 * t + a] - cb.lo[a]) * scale);
                 out.cnt[a][k]++;
                 out.box[a][k].grow(tri_box[t]);
             }
@@ -187,9 +195,7 @@ struct Builder {
             const int a = best_axis;
             const double scale = kBins / (double)(cb.hi[a] - cb.lo[a]);
             auto it = std::partition(refs.begin() + first, refs.begin() + first + count, [&](uint32_t t) {
-                int k = (int)(((double)centroid[3 * t + a] - cb.lo[a]) * scale);
-                k = std::min(std::max(k, 0), kBins - 1);
-                return k <= best_split;
+                return bin_of(((double)centroid[3 * t + a] - cb.lo[a]) * scale) <= best_split;
             });
             mid = (uint32_t)(it - refs.begin());
         } else {
@@ -591,7 +597,8 @@ double flat_sah_cost(const float* bvh, const float* verts)
                      dz = (double)hi[2] - (double)lo[2];
         return dx * dy + dy * dz + dz * dx;
     };
-    double sum = 0.0, root = 0.0;
+    Sum2 sum;                                                   // order-independent: the device's bits (vr_devmesh.hpp)
+    double root = 0.0;
     std::vector<size_t> st{ 0 };                                // node float4 offsets
     while (!st.empty()) {
         const size_t off = st.back();
@@ -603,16 +610,16 @@ double flat_sah_cost(const float* bvh, const float* verts)
         for (int k = 0; k < 3; ++k) { olo[k] = std::min(lo[0][k], lo[1][k]); ohi[k] = std::max(hi[0][k], hi[1][k]); }
         const double own = area(olo, ohi);
         if (off == 0) root = own;
-        sum += own;
+        sum2_add(sum, own);
         for (int c = 0; c < 2; ++c) {
             const int32_t idx = fbits(n[12 + c]);
             if (idx >= 0) { st.push_back((size_t)idx); continue; }
             size_t s = (size_t)(~idx), count = 0;
             while ((uint32_t)fbits(verts[4 * s]) != 0x80000000u) { s += 3; ++count; }
-            sum += area(lo[c], hi[c]) * (double)count;
+            sum2_add(sum, area(lo[c], hi[c]) * (double)count);
         }
     }
-    return root > 0.0 && root < (double)INFINITY ? sum / root : (double)INFINITY;
+    return root > 0.0 && root < (double)INFINITY ? sum.hi / root : (double)INFINITY;
 }
 
 } // namespace vr

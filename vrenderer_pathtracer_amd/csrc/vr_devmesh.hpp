@@ -47,6 +47,24 @@ VR_DEVBVH_HD inline uint16_t half_directed(uint32_t bits, bool up)
     return (uint16_t)(sign | mag);
 }
 
+// A sum of doubles carried as an unevaluated pair hi + lo (|lo| <= ulp(hi) / 2)
+// with error-free additions (Knuth's TwoSum), the running error below 2^-100
+// of the sum: rounded to one double, the sum of a few thousand positive terms
+// depends on the order they were added in only where it lies within that
+// 2^-100 of a rounding boundary, which no test has met and nothing rules out.
+// The SAH cost is summed this way by the host (vr_bvh.cpp flat_sah_cost) and by
+// the device (vr_refit.hip), which walk the nodes in different orders and are
+// compared by bits (tests/test_gpu_extreme.py).  Needs -ffp-contract=off and no fast-math, as the library has.
+struct Sum2 { double hi = 0.0, lo = 0.0; };
+VR_DEVBVH_HD inline void sum2_add(Sum2& s, double x_hi, double x_lo = 0.0)
+{
+    const double t = s.hi + x_hi;
+    const double b = t - s.hi;
+    const double e = ((s.hi - (t - b)) + (x_hi - b)) + (s.lo + x_lo);
+    s.hi = t + e;
+    s.lo = e - (s.hi - t);
+}
+
 // half_directed on n device floats, both directions (vrhip_selftest_half_box)
 int launch_half_box(const float* in, size_t n, uint16_t* down, uint16_t* up, void* stream);
 

@@ -48,11 +48,12 @@ VR_DEVBVH_HD inline double sah_area(const SahBox& b)
     return 2.0 * (dx * dy + dy * dz + dz * dx);
 }
 // the bin of centroid c on an axis whose centroid bounds start at lo and span
-// ext > 0 (vr_bvh.cpp:104-110 and :188-191, the same expression in both)
+// ext > 0 (vr_bvh.cpp Builder::bin_of and its two callers)
 VR_DEVBVH_HD inline int sah_bin(float c, float lo, float ext)
 {
     const double scale = kSahBins / (double)ext;
-    int k = (int)(((double)c - lo) * scale);
+    const double x = ((double)c - lo) * scale;
+    int k = x == x ? (int)x : 0;                  // NaN (an overflowed centroid, scale 0): bin 0, as Builder::bin_of
     k = k < 0 ? 0 : k;
     return k > kSahBins - 1 ? kSahBins - 1 : k;
 }

@@ -45,17 +45,28 @@ inline float fmax_dev(float a, float b)
     return std::signbit(a) ? b : a;
 }
 
+// A slab distance as the device holds it.  Finite rays make NaN slabs (inf - inf
+// once n * inv and o * inv overflow alike), and the integer comparisons below
+// read a NaN's sign.  The device's invalid operations give 0xffc00000, the
+// sign set, as x86's do; other hosts' give 0x7fc00000.  With the sign set, a
+// box that straddles 0 on z (planes -inf and NaN) is missed; with it clear, z
+// would drop out of the span and the box be entered.  Pinned against the
+// device by tests/test_gpu_extreme.py
+// (test_nan_slab_rays_agree_on_device_and_host) and against numpy, whatever
+// the host, by tests/test_extreme_cpu.py.
+inline float slab_dev(float x) { return x != x ? float_of((int32_t)0xffc00000u) : x; }
+
 // spanBeginKepler / spanEndKepler (MathHelpers.cuh:454-552): float min / max
 // per axis, then integer max / min of the bit patterns
 inline float span_begin(float a0, float a1, float b0, float b1, float c0, float c1, float d)
 {
-    const int32_t zc = imax(imin(bits_of(c0), bits_of(c1)), bits_of(d));
-    return float_of(imax(imax(bits_of(fmin_dev(a0, a1)), bits_of(fmin_dev(b0, b1))), zc));
+    const int32_t zc = imax(imin(bits_of(slab_dev(c0)), bits_of(slab_dev(c1))), bits_of(d));
+    return float_of(imax(imax(bits_of(fmin_dev(slab_dev(a0), slab_dev(a1))), bits_of(fmin_dev(slab_dev(b0), slab_dev(b1)))), zc));
 }
 inline float span_end(float a0, float a1, float b0, float b1, float c0, float c1, float d)
 {
-    const int32_t zc = imin(imax(bits_of(c0), bits_of(c1)), bits_of(d));
-    return float_of(imin(imin(bits_of(fmax_dev(a0, a1)), bits_of(fmax_dev(b0, b1))), zc));
+    const int32_t zc = imin(imax(bits_of(slab_dev(c0)), bits_of(slab_dev(c1))), bits_of(d));
+    return float_of(imin(imin(bits_of(fmax_dev(slab_dev(a0), slab_dev(a1))), bits_of(fmax_dev(slab_dev(b0), slab_dev(b1)))), zc));
 }
 
 struct V3 { float x, y, z; };

@@ -115,55 +115,65 @@ __device__ __forceinline__ double area64(const float lo[3], const float hi[3])
     return dx * dy + dy * dz + dz * dx;
 }
 
-// sum of the block's values in a fixed order, valid in thread 0
-__device__ __forceinline__ double block_sum(double v)
+// sum of the block's pairs in a fixed order, valid in thread 0
+__device__ __forceinline__ Sum2 block_sum(Sum2 v)
 {
-    __shared__ double part[kBlock];
-    part[threadIdx.x] = v;
+    __shared__ double part_hi[kBlock], part_lo[kBlock];
+    part_hi[threadIdx.x] = v.hi;
+    part_lo[threadIdx.x] = v.lo;
     __syncthreads();
     for (int o = kBlock / 2; o > 0; o >>= 1) {
-        if ((int)threadIdx.x < o) part[threadIdx.x] += part[threadIdx.x + o];
+        if ((int)threadIdx.x < o) {
+            Sum2 a{ part_hi[threadIdx.x], part_lo[threadIdx.x] };
+            sum2_add(a, part_hi[threadIdx.x + o], part_lo[threadIdx.x + o]);
+            part_hi[threadIdx.x] = a.hi;
+            part_lo[threadIdx.x] = a.lo;
+        }
         __syncthreads();
     }
-    return part[0];
+    return Sum2{ part_hi[0], part_lo[0] };
 }
 
-// per node: the area of its own box, and of each leaf child's box once per triangle
+// per node: the area of its own box, and of each leaf child's box once per
+// triangle; partial[2 b], partial[2 b + 1]: block b's pair
 __global__ __launch_bounds__(kBlock) void refit_cost_kernel(const float4* __restrict__ bvh, uint32_t n_nodes,
                                                             double* __restrict__ partial)
 {
     const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
-    double term = 0.0;
+    Sum2 term;
     if (i < n_nodes) {
         const float4 r0 = bvh[4 * (size_t)i], r1 = bvh[4 * (size_t)i + 1], r2 = bvh[4 * (size_t)i + 2],
                      r3 = bvh[4 * (size_t)i + 3];
         const float lo[2][3] = { { r0.x, r0.z, r2.x }, { r1.x, r1.z, r2.z } };
         const float hi[2][3] = { { r0.y, r0.w, r2.y }, { r1.y, r1.w, r2.w } };
         const DevBox own = own_box(bvh, i);
-        term = area64(own.lo, own.hi);
+        sum2_add(term, area64(own.lo, own.hi));
         const int32_t c[2] = { __float_as_int(r3.x), __float_as_int(r3.y) };
         for (int ch = 0; ch < 2; ++ch) {
             if (c[ch] >= 0) continue;
             uint32_t first, count;
             leaf_range(c[ch], first, count);
-            term += area64(lo[ch], hi[ch]) * (double)count;
+            sum2_add(term, area64(lo[ch], hi[ch]) * (double)count);
         }
     }
     term = block_sum(term);
-    if (threadIdx.x == 0) partial[blockIdx.x] = term;
+    if (threadIdx.x == 0) {
+        partial[2 * (size_t)blockIdx.x] = term.hi;
+        partial[2 * (size_t)blockIdx.x + 1] = term.lo;
+    }
 }
 
 __global__ __launch_bounds__(kBlock) void refit_cost_final_kernel(const float4* __restrict__ bvh,
                                                                   const double* __restrict__ partial,
                                                                   uint32_t n_partial, double* __restrict__ cost)
 {
-    double sum = 0.0;
-    for (uint32_t i = threadIdx.x; i < n_partial; i += kBlock) sum += partial[i];
+    Sum2 sum;
+    for (uint32_t i = threadIdx.x; i < n_partial; i += kBlock) sum2_add(sum, partial[2 * (size_t)i], partial[2 * (size_t)i + 1]);
     sum = block_sum(sum);
     if (threadIdx.x != 0) return;
     const DevBox root = own_box(bvh, 0);
     const double a = area64(root.lo, root.hi);
-    *cost = a > 0.0 && a < (double)__builtin_inff() ? sum / a : (double)__builtin_inff();
+    *cost = a > 0.0 && a < (double)__builtin_inff() ? sum.hi / a : (double)__builtin_inff();
 }
 
 } // namespace

@@ -31,8 +31,10 @@ int refit_apply(const float* positions, const float* normals, const float* tange
                 void* stream);
 
 // SAH cost of the tree (1 per node, 1 per triangle) over the root's area, in
-// fp64 with a fixed summation order: partial holds one double per block of
-// refit_cost_blocks(n_nodes), *cost the result (+inf for a root without area).
+// fp64 with a fixed summation order over pairs (vr_devmesh.hpp Sum2), so the
+// result is, in practice, flat_sah_cost's on the export bit for bit: partial holds two
+// doubles per block of refit_cost_blocks(n_nodes), *cost the result (+inf for
+// a root without area).
 uint32_t refit_cost_blocks(uint32_t n_nodes);
 int refit_sah_cost(const vr4* bvh, uint32_t n_nodes, double* partial, double* cost, void* stream);
 

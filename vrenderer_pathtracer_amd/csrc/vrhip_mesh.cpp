@@ -214,11 +214,11 @@ int vrhip_bvh_sah_cost(vrhip_ctx* c, double* cost)
     if ((rc = svc_close(c)) != VRHIP_OK) return rc;
     const vr::MeshArrays& a = c->mesh.a;
     const uint32_t nb = vr::refit_cost_blocks(a.n_nodes);
-    dev_ptr<double> buf;                          // the block partials, then the result
-    HIP_TRY(dev_alloc(buf, ((size_t)nb + 1) * sizeof(double)));
-    const int e = vr::refit_sah_cost(a.bvh, a.n_nodes, buf.get(), buf.get() + nb, c->stream);
+    dev_ptr<double> buf;                          // the block partials (a pair each), then the result
+    HIP_TRY(dev_alloc(buf, (2 * (size_t)nb + 1) * sizeof(double)));
+    const int e = vr::refit_sah_cost(a.bvh, a.n_nodes, buf.get(), buf.get() + 2 * (size_t)nb, c->stream);
     hipError_t he = e ? (hipError_t)e
-                      : hipMemcpyAsync(cost, buf.get() + nb, sizeof(double), hipMemcpyDeviceToHost, c->stream);
+                      : hipMemcpyAsync(cost, buf.get() + 2 * (size_t)nb, sizeof(double), hipMemcpyDeviceToHost, c->stream);
     if (he == hipSuccess) he = hipStreamSynchronize(c->stream);
     else (void)hipStreamSynchronize(c->stream);
     if (he != hipSuccess) return fail(VRHIP_ERR_HIP, std::string("SAH cost: ") + hipGetErrorString(he));
