@@ -291,6 +291,56 @@ enum { VRHIP_RAYS_CLOSEST = 0, VRHIP_RAYS_ANY = 1 };
 int vrhip_trace_rays(vrhip_ctx *ctx, const float *d_origins /*float[3n]*/, const float *d_dirs /*float[3n]*/,
                      const float *d_tmax /*float[n] or NULL*/, uint32_t n_rays, uint32_t mode,
                      vrhip_ray_hit *d_hits /*[n]*/);
+/* Radiance queries (no reference counterpart as a call: the reference traces
+ * its one camera only): what light arrives along the caller's own rays, for
+ * irradiance probes, lightmap texels and radiance at arbitrary points.  The
+ * reference's trace (cuda/src/PathTracer.cu:597-770) is run along n_rays rays
+ * and one float4 per ray is written.  All arrays are device pointers on the
+ * context's device; d_radiance is 16-byte aligned.
+ *   Scene: the whole scene as vrhip_render would trace it right now -- Cornell
+ *     box, example sphere, BRDF view, the resident mesh (ignored while the
+ *     example sphere is on), texture maps, BRDF table, HDRI, Fresnel
+ *     parameters -- under the flag word vrhip_render computes, walked as
+ *     vrhip_set_strict_traversal says.  A mesh is not required.  The camera,
+ *     the tiling, the frame counter, the accumulation and the images play no
+ *     part and are not touched.
+ *   Ray: the origin is used as given; the direction is normalised by the
+ *     operation the reference applies to its camera ray (:842-844), so a
+ *     caller who passes a pixel's un-normalised camera direction gets that
+ *     pixel's camera ray.  A ray is valid when its six floats are finite and
+ *     the fp32 sum dx*dx + dy*dy + dz*dz is finite and greater than 0.  An
+ *     invalid ray is classified before any scene test; its record is
+ *     {0, 0, 0, 0}.
+ *   Paths: ray i starts from the seed pair (d_seeds[2i], d_seeds[2i+1]) and
+ *     runs n_samples paths one after the other on that seed stream, exactly as
+ *     the reference runs a pixel's two samples of a frame (:620-622): each
+ *     path continues with the seeds the one before left behind.
+ *     1 <= n_samples <= 4096.
+ *   Record: rgb = ((0 + r_0 * c) + r_1 * c) + ... in path order, r_k path k's
+ *     radiance and c = 1.f / (float)n_samples, every product and sum rounded
+ *     in fp32: for n_samples = 2, bit for bit what the reference adds to a
+ *     pixel in one frame (seeds (x * frame, y * time)).  w is the last path's
+ *     result.w, the depth term: the depth image would show
+ *     f2u8((1 - w) * 255).
+ *   Range: rays are traced as the render traces its own.  Parity with the CPU
+ *     oracle is pinned for origins at scene scale (tests/test_gpu_radiance.py);
+ *     the extreme-float rules of vrhip_trace_rays (the strict walk for far
+ *     origins, large coordinates and tiny direction components) are NOT
+ *     applied here: a ray far outside the scene is walked like a camera ray
+ *     placed there, and a record outside the tested range may hold NaNs.
+ *   Cost: one ray per GPU lane; a lane whose paths end early idles until the
+ *     slowest of its 64 neighbours has finished (no path pool for ray buffers).
+ * The work runs on the context stream and the call returns when it has
+ * finished.  n_rays == 0: VRHIP_OK, nothing written.  VRHIP_ERR_INVALID,
+ * before any device call, for a null ctx, a null array with n_rays > 0, a
+ * misaligned d_radiance, n_samples outside [1, 4096], and a
+ * vrhip_create_multi context (the pointers live on one device).
+ * VRHIP_ERR_NO_ENV in HDRI mode without an environment map, as vrhip_render.
+ * Added without an ABI version change (ABI 6 gained this symbol and changed
+ * no other). */
+int vrhip_trace_radiance(vrhip_ctx *ctx, const float *d_origins /*float[3n]*/, const float *d_dirs /*float[3n]*/,
+                         const uint32_t *d_seeds /*uint32[2n]*/, uint32_t n_rays, uint32_t n_samples,
+                         float *d_radiance /*float4[n], 16-byte aligned*/);
 /* replaces vRendererCuda::loadHDR (src/vRendererCuda.cpp:320-340) +
  * cu_setHDRDim: rgba float4[w*h] (or half4 with the _half variant, the
  * Imf::Rgba layout, converted on the device). */
@@ -454,7 +504,7 @@ int vrhip_set_overlap(vrhip_ctx *ctx, int mode);
  *   vrhip_gl_present, vrhip_pack_tiles/unpack_tiles, vrhip_last_kernel_ms,
  *   vrhip_kernel_stats, vrhip_debug_counters, vrhip_set_camera, vrhip_clear,
  *   every upload (vrhip_upload_mesh_device too), vrhip_refit_mesh_device,
- *   vrhip_bvh_sah_cost, vrhip_export_mesh_flat, vrhip_trace_rays, vrhip_set_stream, vrhip_set_tiling, vrhip_set_service
+ *   vrhip_bvh_sah_cost, vrhip_export_mesh_flat, vrhip_trace_rays, vrhip_trace_radiance, vrhip_set_stream, vrhip_set_tiling, vrhip_set_service
  *   (and its timing / budget hooks), vrhip_comm_init/destroy, vrhip_destroy,
  *   the counting renders, and a vrhip_render that does not fit the session.
  *   Calls that do NOT close it: the flag setters (Cornell box, example sphere,

@@ -2,7 +2,10 @@
 # VGPRs / spills / scratch of the production path-kernel instantiations in a
 # build_variants log (kernel-resource-usage remarks):
 #   bash scripts/kres.sh variants/<name>.log
-python3 - "$1" <<'PY'
+# With a second argument `radiance`: every instantiation of the radiance query
+# kernel (vr_radiance*.hip) beside render_kernel of the same feature set:
+#   bash scripts/kres.sh variants/<name>.log radiance
+python3 - "$1" "$2" <<'PY'
 import re, sys
 recs, cur = {}, None
 for line in open(sys.argv[1]):
@@ -10,9 +13,27 @@ for line in open(sys.argv[1]):
     if m:
         cur = recs.setdefault(m.group(1), {})
         continue
-    m = re.search(r"remark:\s+(VGPRs|VGPRs Spill|SGPRs Spill|ScratchSize \[bytes/lane\]|Occupancy \[waves/SIMD\]): (\d+)", line)
+    m = re.search(r"remark:\s+(VGPRs|VGPRs Spill|SGPRs Spill|ScratchSize \[bytes/lane\]|Occupancy \[waves/SIMD\]|LDS Size \[bytes/block\]): (\d+)", line)
     if m and cur is not None and m.group(1) not in cur:
         cur[m.group(1)] = int(m.group(2))
+if len(sys.argv) > 2 and sys.argv[2] == "radiance":
+    CLS, ALL = 1 << 30, 511
+    sets = [("class Cornell+mesh", CLS + 253, (16, 24, 32, 64)), ("class HDRI+mesh", CLS + 252, (16, 24, 32, 64)),
+            ("generic (strict)", ALL, (16, 24, 32, 64)), ("class Cornell spheres", CLS + 247, (16,)),
+            ("class HDRI spheres", CLS + 246, (16,))]
+    cols = ("VGPRs", "VGPRs Spill", "SGPRs Spill", "ScratchSize [bytes/lane]", "LDS Size [bytes/block]", "Occupancy [waves/SIMD]")
+    print(f"{'kernel':44s} {'VGPRs':>5s} {'vspill':>6s} {'sspill':>6s} {'scratch':>7s} {'LDS':>6s} {'waves':>5s}")
+    def row(lab, name):
+        r = recs.get(name)
+        if r is None:
+            print(f"{lab:44s} (not in this build)")
+        else:
+            print(f"{lab:44s} " + " ".join(f"{r.get(c, 0):{w}d}" for c, w in zip(cols, (5, 6, 6, 7, 6, 5))))
+    for lab, feat, stacks in sets:
+        row(f"render_kernel<16> {lab}", f"_ZN2vr13render_kernelILi16ELb0ELj{feat}EEEvNS_12RenderParamsE")
+        for st in stacks:
+            row(f"  ray_radiance_kernel<{st}> {lab}", f"_ZN2vr19ray_radiance_kernelILi{st}ELj{feat}EEEvNS_12RenderParamsENS_11RayRadianceE")
+    sys.exit(0)
 E, INL, SML, SVC, SPA = 2147483648, 8192, 16384, 32768, 65536
 C2, C3, C5 = E + 9, E + 232, E + 8
 CLS_C, CLS_H = (1 << 30) + 253, (1 << 30) + 252

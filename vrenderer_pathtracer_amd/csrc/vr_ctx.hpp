@@ -1,4 +1,4 @@
-// vr_ctx.hpp -- internal to the host half of libvrhip.so (vrhip_scene, _mesh, _service, _render, _multi
+// vr_ctx.hpp -- internal to the host half of libvrhip.so (vrhip_scene, _mesh, _query, _service, _render, _multi
 // and _selftest.cpp, which implement include/vrhip.h): the context, the resident mesh it owns, the error
 // helpers and the functions one unit calls in another.  The host half is the device-side counterpart of
 // vRendererCuda (src/vRendererCuda.cpp) and the cu_* device ABI (cuda/include/PathTracer.cuh:107-165), re-designed
@@ -351,6 +351,32 @@ inline void mesh_params(const ResidentMesh& m, vr::RenderParams& p)
     p.bvh = a.bvh; p.bvh16 = a.bvh16; p.verts = a.verts; p.tri_e = a.tri_e; p.tpath = a.tpath;
     p.normals = a.normals; p.tangents = a.tangents; p.uvs = a.uvs;
     p.n_nodes = a.n_nodes; p.n_tris = a.n_refs;
+}
+
+// The scene half of a launch's parameters, what a path reads once it has its
+// ray: the flag word, the mesh, the environment, the texture maps, the BRDF
+// table and the Fresnel parameters.  vrhip_render (build_params) and
+// vrhip_trace_radiance trace the same scene through it.
+inline void scene_params(const vrhip_ctx* c, vr::RenderParams& p)
+{
+    p.fresnel_coef = c->fresnel_coef; p.fresnel_pow = c->fresnel_pow;
+    uint32_t f = 0;
+    if (c->cornell) f |= vr::F_CORNELL;
+    if (c->example) f |= vr::F_EXAMPLE;
+    if (c->view_brdf) f |= vr::F_VIEW_BRDF;
+    if (c->strict) f |= vr::F_STRICT;
+    // the reference skips the mesh while the example sphere is on
+    // (PathTracer.cu:192,268): a sphere scene, whatever mesh is loaded
+    if (c->mesh.loaded() && !c->example) f |= vr::F_MESH;
+    if (c->brdf) f |= vr::F_BRDF;
+    if (c->tex[0]) f |= vr::F_TEX_DIFF;
+    if (c->tex[1]) f |= vr::F_TEX_NORM;
+    if (c->tex[2]) f |= vr::F_TEX_SPEC;
+    p.flags = f;
+    mesh_params(c->mesh, p);
+    p.hdr = c->hdr; p.hdr_w = c->hdr_w; p.hdr_h = c->hdr_h;
+    for (int i = 0; i < 3; ++i) { p.tex[i] = c->tex[i]; p.tex_w[i] = c->tex_w[i]; p.tex_h[i] = c->tex_h[i]; }
+    p.brdf = c->brdf;
 }
 
 // traversal stack entries for a tree of this depth (the walk needs depth + 1),

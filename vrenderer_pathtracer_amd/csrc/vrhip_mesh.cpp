@@ -1,6 +1,7 @@
 // vrhip_mesh.cpp -- the resident triangle mesh (vr_ctx.hpp ResidentMesh): the
-// host and the device upload, the refit, SAH costs, ray queries, the export,
-// and the calls on flattened trees that need no context (include/vrhip.h).
+// host and the device upload, the refit, SAH costs, the export, and the calls
+// on flattened trees that need no context (include/vrhip.h).  The queries
+// along the caller's rays on the device: vrhip_query.cpp.
 #include <cstring>
 
 #include "vr_bvh.hpp"
@@ -232,35 +233,6 @@ int vrhip_flat_sah_cost(const float* bvh, size_t n_bvh_f4, const float* verts, s
     if (v != 0) return fail(VRHIP_ERR_BVH, "validation failed (code " + std::to_string(v) + ")");
     *cost = vr::flat_sah_cost(bvh, verts);
     return VRHIP_OK;
-}
-
-// Ray queries against the resident mesh (vr_rayquery.hip): the path kernels'
-// traversal fed from the caller's ray buffer.  Reads the mesh only; the
-// accumulation, the images and the frame counter stay as they are.
-static_assert(sizeof(vrhip_ray_hit) == 16 && sizeof(vr::RayHit) == 16, "one 16-B record per ray");
-int vrhip_trace_rays(vrhip_ctx* c, const float* d_origins, const float* d_dirs, const float* d_tmax, uint32_t n_rays,
-                     uint32_t mode, vrhip_ray_hit* d_hits)
-{
-    if (!c) return fail(VRHIP_ERR_INVALID, "null ctx");
-    if (mode != VRHIP_RAYS_CLOSEST && mode != VRHIP_RAYS_ANY) return fail(VRHIP_ERR_INVALID, "unknown ray query mode");
-    if (n_rays > 0 && (!d_origins || !d_dirs || !d_hits)) return fail(VRHIP_ERR_INVALID, "null ray or hit array");
-    if (((uintptr_t)d_hits & 15u) != 0u) return fail(VRHIP_ERR_INVALID, "d_hits is not 16-byte aligned");
-    if (!c->group.empty()) return refuse_multi(c, "vrhip_trace_rays");
-    if (!c->mesh.loaded()) return fail(VRHIP_ERR_INVALID, "no mesh loaded");
-    if (n_rays == 0) return VRHIP_OK;
-    int rc = set_device(c); if (rc) return rc;
-    if ((rc = svc_close(c)) != VRHIP_OK) return rc;
-    vr::RenderParams p;
-    std::memset(&p, 0, sizeof(p));
-    mesh_params(c->mesh, p);
-    p.verts = nullptr; p.normals = nullptr; p.tangents = nullptr; p.uvs = nullptr;   // a query shades nothing
-    p.flags = vr::F_MESH | (c->strict ? (uint32_t)vr::F_STRICT : 0u);
-    const vr::RayQuery q{ d_origins, d_dirs, d_tmax, n_rays, mode == VRHIP_RAYS_ANY ? 1u : 0u, c->mesh.a.prim_id,
-                          (vr::RayHit*)d_hits };
-    const int e = vr::launch_ray_query(p, q, mesh_stack_entries(c->mesh.a.depth), c->cu_count, c->stream);
-    if (e) return fail(VRHIP_ERR_HIP, std::string("ray query: ") + hipGetErrorString((hipError_t)e));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    return svc_verify(c);
 }
 
 int vrhip_flat_trace_rays(const float* bvh, size_t n_bvh_f4, const float* verts, size_t n_slots, const float* origins,

@@ -1,0 +1,70 @@
+// vrhip_query.cpp -- the queries along the caller's own rays on the device
+// (include/vrhip.h): where a ray hits the resident mesh (vrhip_trace_rays,
+// vr_rayquery.hip) and what light arrives along it (vrhip_trace_radiance,
+// vr_radiance.hip).  Both read the scene only: the accumulation, the images
+// and the frame counter stay as they are.
+#include <cstring>
+
+#include "vr_ctx.hpp"
+#include "vr_radiance.hpp"
+#include "vr_rayquery.hpp"
+
+// Ray queries against the resident mesh: the path kernels' traversal fed from
+// the caller's ray buffer.
+static_assert(sizeof(vrhip_ray_hit) == 16 && sizeof(vr::RayHit) == 16, "one 16-B record per ray");
+int vrhip_trace_rays(vrhip_ctx* c, const float* d_origins, const float* d_dirs, const float* d_tmax, uint32_t n_rays,
+                     uint32_t mode, vrhip_ray_hit* d_hits)
+{
+    if (!c) return fail(VRHIP_ERR_INVALID, "null ctx");
+    if (mode != VRHIP_RAYS_CLOSEST && mode != VRHIP_RAYS_ANY) return fail(VRHIP_ERR_INVALID, "unknown ray query mode");
+    if (n_rays > 0 && (!d_origins || !d_dirs || !d_hits)) return fail(VRHIP_ERR_INVALID, "null ray or hit array");
+    if (((uintptr_t)d_hits & 15u) != 0u) return fail(VRHIP_ERR_INVALID, "d_hits is not 16-byte aligned");
+    if (!c->group.empty()) return refuse_multi(c, "vrhip_trace_rays");
+    if (!c->mesh.loaded()) return fail(VRHIP_ERR_INVALID, "no mesh loaded");
+    if (n_rays == 0) return VRHIP_OK;
+    int rc = set_device(c); if (rc) return rc;
+    if ((rc = svc_close(c)) != VRHIP_OK) return rc;
+    vr::RenderParams p;
+    std::memset(&p, 0, sizeof(p));
+    mesh_params(c->mesh, p);
+    p.verts = nullptr; p.normals = nullptr; p.tangents = nullptr; p.uvs = nullptr;   // a query shades nothing
+    p.flags = vr::F_MESH | (c->strict ? (uint32_t)vr::F_STRICT : 0u);
+    const vr::RayQuery q{ d_origins, d_dirs, d_tmax, n_rays, mode == VRHIP_RAYS_ANY ? 1u : 0u, c->mesh.a.prim_id,
+                          (vr::RayHit*)d_hits };
+    const int e = vr::launch_ray_query(p, q, mesh_stack_entries(c->mesh.a.depth), c->cu_count, c->stream);
+    if (e) return fail(VRHIP_ERR_HIP, std::string("ray query: ") + hipGetErrorString((hipError_t)e));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return svc_verify(c);
+}
+
+// Radiance along the caller's rays: the whole scene as vrhip_render would
+// trace it now (scene_params), the path tracer entered from a ray buffer
+// instead of the camera.  The checks come in vrhip_render's order: the
+// arguments, nothing to do, the environment, then the device.
+static_assert(sizeof(vr::vr4) == 16, "one float4 per ray");
+int vrhip_trace_radiance(vrhip_ctx* c, const float* d_origins, const float* d_dirs, const uint32_t* d_seeds,
+                         uint32_t n_rays, uint32_t n_samples, float* d_radiance)
+{
+    if (!c) return fail(VRHIP_ERR_INVALID, "null ctx");
+    if (n_rays > 0 && (!d_origins || !d_dirs || !d_seeds || !d_radiance))
+        return fail(VRHIP_ERR_INVALID, "null ray, seed or radiance array");
+    if (((uintptr_t)d_radiance & 15u) != 0u) return fail(VRHIP_ERR_INVALID, "d_radiance is not 16-byte aligned");
+    if (n_samples < 1u || n_samples > vr::kRadianceMaxSamples)
+        return fail(VRHIP_ERR_INVALID, "n_samples is " + std::to_string(n_samples) + " (1 to " +
+                                           std::to_string(vr::kRadianceMaxSamples) + ")");
+    if (!c->group.empty()) return refuse_multi(c, "vrhip_trace_radiance");
+    if (n_rays == 0) return VRHIP_OK;
+    if (!c->cornell && !c->hdr)
+        return fail(VRHIP_ERR_NO_ENV, "HDRI mode needs an environment map (vrhip_upload_hdr)");
+    int rc = set_device(c); if (rc) return rc;
+    if ((rc = svc_close(c)) != VRHIP_OK) return rc;
+    vr::RenderParams p;
+    std::memset(&p, 0, sizeof(p));
+    scene_params(c, p);
+    const vr::RayRadiance q{ d_origins, d_dirs, d_seeds, n_rays, n_samples, (vr4*)d_radiance };
+    (void)hipGetLastError();            // the launch below reports its own error only
+    const int e = vr::launch_ray_radiance(p, q, mesh_stack_entries(c->mesh.a.depth), c->cu_count, c->stream);
+    if (e) return fail(VRHIP_ERR_HIP, std::string("radiance query: ") + hipGetErrorString((hipError_t)e));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return svc_verify(c);
+}

@@ -263,8 +263,8 @@ struct RenderCall {
     bool wave_kernel;            // mesh scenes: the path-pool kernel (scratch + finish pass)
 };
 
-// The launch parameters that come from the context: camera, flags, scene and
-// frame buffers, tiling, and the traversal stack depth.
+// The launch parameters that come from the context: camera, scene
+// (scene_params), frame buffers, tiling, and the traversal stack depth.
 static void build_params(const vrhip_ctx* c, RenderCall& q)
 {
     vr::RenderParams& p = q.p;
@@ -279,30 +279,13 @@ static void build_params(const vrhip_ctx* c, RenderCall& q)
     p.cam_sxy = c->cam_sxy;
     p.tone_t = c->tone_t;
     p.wr = (c->W / 16u) * 16u; p.hr = rendered_rows(c);
-    p.fresnel_coef = c->fresnel_coef; p.fresnel_pow = c->fresnel_pow;
-    uint32_t f = 0;
-    if (c->cornell) f |= vr::F_CORNELL;
-    if (c->example) f |= vr::F_EXAMPLE;
-    if (c->view_brdf) f |= vr::F_VIEW_BRDF;
-    if (c->strict) f |= vr::F_STRICT;
-    // the reference skips the mesh while the example sphere is on
-    // (PathTracer.cu:192,268): a sphere scene, whatever mesh is loaded
-    if (c->mesh.loaded() && !c->example) f |= vr::F_MESH;
-    if (c->brdf) f |= vr::F_BRDF;
-    if (c->tex[0]) f |= vr::F_TEX_DIFF;
-    if (c->tex[1]) f |= vr::F_TEX_NORM;
-    if (c->tex[2]) f |= vr::F_TEX_SPEC;
-    p.flags = f;
+    scene_params(c, p);
     p.tiles_x = p.wr / 16u;
     p.rank = c->rank; p.nranks = c->nranks;
-    mesh_params(c->mesh, p);
-    p.hdr = c->hdr; p.hdr_w = c->hdr_w; p.hdr_h = c->hdr_h;
-    for (int i = 0; i < 3; ++i) { p.tex[i] = c->tex[i]; p.tex_w[i] = c->tex_w[i]; p.tex_h[i] = c->tex_h[i]; }
-    p.brdf = c->brdf;
     p.accum = c->accum; p.rgba = c->rgba; p.depth = c->depth;
     q.n_tiles = owned_tiles_of(c->W, c->H, c->rank, c->nranks);
     q.stack = mesh_stack_entries(c->mesh.a.depth);
-    q.wave_kernel = (f & vr::F_MESH) != 0u;
+    q.wave_kernel = (p.flags & vr::F_MESH) != 0u;
 }
 
 // The service attempt: whether this call's launches go to the render service

@@ -383,6 +383,42 @@ class VRendererHIP:
                                          ctypes.c_void_p(rec.data_ptr())), "vrhip_trace_rays")
         return _unpack_hits(rec, torch)
 
+    def traceRadiance(self, origins, dirs, seeds=None, samples: int = 2):
+        """What light arrives along these rays (vrhip_trace_radiance)?  The
+        whole scene as render() would trace it now; the camera, the
+        accumulation, the images and the frame counter play no part.
+        origins, dirs: (N,3) float32 torch tensors on the renderer's GPU,
+        contiguous; directions are normalised by the library.  seeds: (N,2)
+        uint32 or int32, the seed pair each ray's first path starts from;
+        None draws them with torch.randint on that device.  samples: paths
+        per ray (1 to 4096), run one after the other on the ray's seed stream.
+        Returns an (N,4) float32 device tensor: rgb the mean radiance of the
+        paths, w the last path's depth term; a ray with a non-finite float or
+        a direction of zero or overflowing length gives (0,0,0,0).
+        ValueError for a wrong device, dtype, shape or layout.  Synchronises
+        torch's current stream first; the query runs on the renderer's own
+        stream and has finished on return."""
+        import torch
+        self._need_ctx()
+        dev = self._torch_device()
+        int_types = tuple(t for t in (torch.int32, getattr(torch, "uint32", None)) if t is not None)
+        ptr = self._tensor_ptr
+        p_o = ptr("origins", origins, 3, (torch.float32,))
+        if p_o is None:
+            raise ValueError("origins and dirs are required")
+        n = int(origins.shape[0])
+        p_d = ptr("dirs", dirs, 3, (torch.float32,), n)
+        if p_d is None:
+            raise ValueError("origins and dirs are required")
+        if seeds is None:
+            seeds = torch.randint(-2**31, 2**31, (n, 2), dtype=torch.int32, device=f"cuda:{dev}")
+        p_s = ptr("seeds", seeds, 2, int_types, n)
+        out = torch.empty((n, 4), dtype=torch.float32, device=f"cuda:{dev}")
+        torch.cuda.current_stream(dev).synchronize()
+        check(self._lib.vrhip_trace_radiance(self._ctx, p_o, p_d, p_s, n, int(samples),
+                                             ctypes.c_void_p(out.data_ptr())), "vrhip_trace_radiance")
+        return out
+
     def _torch_device(self) -> int:
         """The GPU index device tensors must live on (a group's first device)."""
         if isinstance(self._device, (list, tuple)):
