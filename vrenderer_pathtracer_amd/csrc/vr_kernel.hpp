@@ -130,6 +130,54 @@ __device__ __forceinline__ float sphere_intersect(const Sph& s, const Ray& r) {
     return (t = b - det) > eps ? t : ((t = b + det) > eps ? t : 0.0f);
 }
 
+// Sphere::intersect in two parts, for the straight-line set-up pass
+// (intersect_spheres): every sphere's b and det, then every root and select,
+// in one basic block -- the tests have no control dependence, and apart the
+// scheduler fills one sphere's transcendental and v_cmp -> v_cndmask slots
+// with another's arithmetic.  The operations and their order are
+// sphere_intersect's; a miss is +inf instead of 0 (a hit is > eps and
+// finite), so that the fold is a minimum.
+__device__ __forceinline__ void sphere_b_det(const Sph& s, const Ray& r, float& b, float& det) {
+    const vr4 op = sub4(mk4(s.px, s.py, s.pz, 0.f), r.o);
+    b = dot4(op, r.d);
+    det = b * b - dot4(op, op) + s.r * s.r;
+}
+// The tail without a range vote and without a test of det's sign: sqrt_rn
+// on det as it is, for a det that is not NaN and at most FLT_MAX
+// (straight_ray).  The outcome is sphere_intersect's:
+//   * det >= 2^-96: sqrt_rn is sqrtf (vr_math.hpp);
+//   * det < 0: v_sqrt_f32 returns NaN, both neighbour patterns of a NaN are
+//     NaNs, every compare of sqrt_rn fails and it returns the NaN; b - NaN
+//     and b + NaN fail `> eps`: a miss, as the reference's early return;
+//   * det = -0: v_sqrt_f32 returns -0, sqrt_rn's compares fail (a NaN
+//     residual, and -0 > 0) and it returns -0: t = b, as with sqrtf(-0);
+//   * 0 <= det < 2^-96, where sqrtf(det) lies in [0, 2^-48]: sqrt_rn returns
+//     some s' in [0, 2^-47] -- the hardware root of a normal det is within
+//     one ulp and sqrt_rn moves it by at most one more; a denormal det is
+//     read as such or as 0, and sqrt_rn(0) is 0 or the smallest denormal.
+//     If b <= 2^-14, then b - s <= b + s <= 2^-14 + 2^-47 < eps for every s in
+//     [0, 2^-47]: a miss with sqrtf's root and with s'.  If b > 2^-14, the
+//     floats next to b are at least 2^-39 away (2^-38 above, half of that
+//     below a power of two), more than twice any such s, so b - s and b + s
+//     round to b and the select returns the same b with either root.
+// tests/test_sphere_guard_cpu.py sweeps that argument in fp32.
+__device__ __forceinline__ float sphere_tail(float b, float det) {
+    const float eps = (float)1e-4;
+    const float s = sqrt_rn(det);
+    const float t0 = b - s, t1 = b + s;
+    return t0 > eps ? t0 : (t1 > eps ? t1 : __builtin_inff());
+}
+// The rays sphere_tail is exact for: |o.x| + |o.y| + |o.z| <= 2^40 and
+// |d.x| + |d.y| + |d.z| <= 2^20 (a NaN or an infinity fails the compare).
+// The scene's spheres have |centre| < 2^17 and r <= 1e5, so every |op| is
+// below 2^41, |b| below 3 * 2^61, b * b below 2^126, dot(op, op) below 2^84:
+// det is finite (no NaN: no infinite operand), below 2^127, as sphere_tail
+// asks, and every t of a hit is finite.
+__device__ __forceinline__ bool straight_ray(const Ray& r) {
+    return __builtin_fabsf(r.o.x) + __builtin_fabsf(r.o.y) + __builtin_fabsf(r.o.z) <= 0x1p40f &&
+           __builtin_fabsf(r.d.x) + __builtin_fabsf(r.d.y) + __builtin_fabsf(r.d.z) <= 0x1p20f;
+}
+
 enum HitKind { HK_NONE = 0, HK_CORNELL = 1, HK_SMALL = 2, HK_EXAMPLE = 3, HK_MESH = 4 };
 struct HitRec {
     float t;
@@ -155,6 +203,26 @@ struct Cnt {
 // exactly what vrhip_render runs and count the memory operations issued.
 template <bool COUNT, uint32_t FEAT>
 __device__ constexpr bool ref_alg() { return COUNT && (FEAT & F_COUNT_EXEC) == 0u; }
+
+// The straight-line sphere tests (intersect_spheres), the vote-free root of
+// a draw (draw_root) and trav_init's one-compare vote: the specialised
+// production kernels of Cornell-box scenes (C2 +2.1 %, C1 +4.7 %).  The
+// generic kernel (which also serves the strict walk) and the reference-
+// algorithm counting variant keep the per-sphere tests.  So do the HDRI
+// kernels, which have no walls to test: with the straight form of their two
+// small spheres C5 stayed where it was, C3 lost about its own spread (2 %),
+// C4's kernel spilled 4 more VGPRs and C5's one-frame kernel one; they
+// compile to what they were.
+template <bool COUNT, uint32_t FEAT>
+__device__ constexpr bool straight_spheres() {
+    return !ref_alg<COUNT, FEAT>() && (FEAT & (F_EXACT | F_CLASS)) != 0u && (FEAT & F_CORNELL) != 0u;
+}
+// The root of a uniform draw or of one minus it (sqrt_draw, vr_math.hpp)
+template <uint32_t FEAT>
+__device__ __forceinline__ float draw_root(float x) {
+    if constexpr (straight_spheres<false, FEAT>()) return sqrt_draw(x);
+    else return sqrt_exact(x);
+}
 
 // One wave-level reduction and one 64-bit atomic per counter per wave.
 __device__ __forceinline__ void flush_counts(const RenderParams& p, const Cnt& cnt, int lane, bool exec)
@@ -289,8 +357,13 @@ __device__ __forceinline__ void trav_init(const RenderParams& p, const Ray& r, f
     const float dx = __builtin_fabsf(r.d.x) > VR_EPS ? r.d.x : VR_EPS;
     const float dy = __builtin_fabsf(r.d.y) > VR_EPS ? r.d.y : VR_EPS;
     const float dz = __builtin_fabsf(r.d.z) > VR_EPS ? r.d.z : VR_EPS;
-    if (__builtin_expect(__ballot(!(__builtin_fabsf(dx) <= kRcpRnHi && __builtin_fabsf(dy) <= kRcpRnHi &&
-                                    __builtin_fabsf(dz) <= kRcpRnHi)) != 0ull, 0)) {
+    // (one compare for the three where the kernel takes it, straight_spheres:
+    // none is a NaN -- a NaN fails `> VR_EPS` above and became +eps -- so
+    // the largest magnitude decides)
+    const bool wide = straight_spheres<false, FEAT>()
+        ? !(__builtin_fmaxf(__builtin_fmaxf(__builtin_fabsf(dx), __builtin_fabsf(dy)), __builtin_fabsf(dz)) <= kRcpRnHi)
+        : !(__builtin_fabsf(dx) <= kRcpRnHi && __builtin_fabsf(dy) <= kRcpRnHi && __builtin_fabsf(dz) <= kRcpRnHi);
+    if (__builtin_expect(__ballot(wide) != 0ull, 0)) {
         tr.ivx = 1.f / dx; tr.ivy = 1.f / dy; tr.ivz = 1.f / dz;
     } else {
         tr.ivx = rcp_rn(dx); tr.ivy = rcp_rn(dy); tr.ivz = rcp_rn(dz);
@@ -612,17 +685,54 @@ __device__ __forceinline__ bool intersect_spheres(const RenderParams& p, const R
 {
     if (COUNT) cnt.rays++;
     hr.t = 1e20f; hr.kind = HK_NONE; hr.idx = 0; hr.bu = hr.bv = 0.f; hr.su = hr.sv = 0.f;
-    if HAS(F_CORNELL) {
+    bool straight = false;
+    if constexpr (straight_spheres<COUNT, FEAT>()) {
+        // one vote per pass instead of one per sphere (sphere_intersect's
+        // sqrt_exact): a wave holding a ray outside straight_ray's bounds --
+        // none that starts inside a scene does -- takes the per-sphere code below
+        straight = __builtin_expect(__ballot(!straight_ray(r)) == 0ull, 1);
+        if (straight) {
+            float t = 1e20f;
+            int code = 0;                                     // kind << 4 | idx through the fold
+            if HAS(F_CORNELL) {
+                float b[6], det[6], d[6];
 #pragma unroll
-        for (int i = 0; i < 6; ++i) {
-            const float dist = sphere_intersect(cornell_sphere(i), r);
-            if (dist != 0.f && dist < hr.t) { hr.t = dist; hr.kind = HK_CORNELL; hr.idx = i; }
+                for (int i = 0; i < 6; ++i) sphere_b_det(cornell_sphere(i), r, b[i], det[i]);
+#pragma unroll
+                for (int i = 0; i < 6; ++i) d[i] = sphere_tail(b[i], det[i]);
+                // the closest, then its index: the first in index order among
+                // equal distances, as the reference's strict < keeps it
+                t = __builtin_fminf(__builtin_fminf(__builtin_fminf(d[0], d[1]), __builtin_fminf(d[2], d[3])),
+                                    __builtin_fminf(__builtin_fminf(d[4], d[5]), t));
+#pragma unroll
+                for (int i = 5; i >= 0; --i)
+                    if (d[i] == t) code = HK_CORNELL << 4 | i;
+            }
+            // the small spheres, which most waves miss entirely, share one skip
+            float b0, det0, b1, det1;
+            sphere_b_det(small_sphere(0), r, b0, det0);
+            sphere_b_det(small_sphere(1), r, b1, det1);
+            if (__ballot(!(det0 < 0) || !(det1 < 0)) != 0ull) {
+                const float d0 = sphere_tail(b0, det0), d1 = sphere_tail(b1, det1);
+                if (d0 < t) { t = d0; code = HK_SMALL << 4 | 0; }
+                if (d1 < t) { t = d1; code = HK_SMALL << 4 | 1; }
+            }
+            hr.t = t; hr.kind = code >> 4; hr.idx = code & 15;   // unpacked before anything reads hr
         }
     }
+    if (!straight) {
+        if HAS(F_CORNELL) {
 #pragma unroll
-    for (int i = 0; i < 2; ++i) {
-        const float dist = sphere_intersect(small_sphere(i), r);
-        if (dist != 0.f && dist < hr.t) { hr.t = dist; hr.kind = HK_SMALL; hr.idx = i; }
+            for (int i = 0; i < 6; ++i) {
+                const float dist = sphere_intersect(cornell_sphere(i), r);
+                if (dist != 0.f && dist < hr.t) { hr.t = dist; hr.kind = HK_CORNELL; hr.idx = i; }
+            }
+        }
+#pragma unroll
+        for (int i = 0; i < 2; ++i) {
+            const float dist = sphere_intersect(small_sphere(i), r);
+            if (dist != 0.f && dist < hr.t) { hr.t = dist; hr.kind = HK_SMALL; hr.idx = i; }
+        }
     }
     if HAS(F_EXAMPLE) {
         const float dist = sphere_intersect(example_sphere(), r);
@@ -1025,8 +1135,8 @@ __device__ __forceinline__ bool bounce_step(const RenderParams& p, Ray& ray, con
         su0 = srng.uniform();
         const float rand1 = 2.f * VR_PI * srng.uniform();
         const float rand2 = srng.uniform();
-        srand2s = sqrt_exact(rand2);
-        srand1m = sqrt_exact(1 - rand2);
+        srand2s = draw_root<FEAT>(rand2);
+        srand1m = draw_root<FEAT>(1 - rand2);
         sincos_p(rand1, &ssn, &scs);
     };
     if constexpr (SPEC && VR_SPEC_SAMPLE == 2) spec_sample();
@@ -1103,13 +1213,13 @@ __device__ __forceinline__ bool bounce_step(const RenderParams& p, Ray& ray, con
             float rand1 = 2.f * VR_PI * ps.rng.uniform();
             float rand2 = ps.rng.uniform();
             probe_coherent(rand1, rand2);
-            const float rand2s = sqrt_exact(rand2);
+            const float rand2s = draw_root<FEAT>(rand2);
             const vr4 u = normalize4(cross4(axis, w));
             const vr4 v = cross4(w, u);
             float sn, cs;
             sincos_p(rand1, &sn, &cs);
             newdir = normalize4(add4(add4(mul4s(mul4s(u, cs), rand2s), mul4s(mul4s(v, sn), rand2s)),
-                                     mul4s(w, sqrt_exact(1 - rand2))));
+                                     mul4s(w, draw_root<FEAT>(1 - rand2))));
             muleq4(ps.mask, h.col);
             muleq4s(ps.mask, dot4(newdir, normal));
             muleq4s(ps.mask, 2.f);
@@ -1122,13 +1232,13 @@ __device__ __forceinline__ bool bounce_step(const RenderParams& p, Ray& ray, con
         float rand1 = 2.f * VR_PI * ps.rng.uniform();
         float rand2 = ps.rng.uniform();
         probe_coherent(rand1, rand2);
-        const float rand2s = sqrt_exact(rand2);
+        const float rand2s = draw_root<FEAT>(rand2);
         const vr4 u = normalize4(cross4(axis, w));
         const vr4 v = cross4(w, u);
         float sn, cs;
         sincos_p(rand1, &sn, &cs);
         const vr4 newdir = normalize4(add4(add4(mul4s(mul4s(u, cs), rand2s), mul4s(mul4s(v, sn), rand2s)),
-                                           mul4s(w, sqrt_exact(1 - rand2))));
+                                           mul4s(w, draw_root<FEAT>(1 - rand2))));
         if HAS(F_BRDF) {
             const float dw = 24 * pow_p(newdir.x * newdir.x + newdir.y * newdir.y + newdir.z * newdir.z, -1.5f);
             if (COUNT) { cnt.brdf++; cnt.ld96 += 1; }

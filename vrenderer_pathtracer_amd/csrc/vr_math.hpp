@@ -307,6 +307,14 @@ __device__ __forceinline__ float sqrt_rn(float x)
     return rp > 0.0f ? sp : t;
 }
 constexpr float kSqrtRnLo = 0x1p-96f;
+// sqrt_rn is also sqrtf at +0: v_sqrt_f32(+0) = +0, the lower neighbour is a
+// NaN pattern whose residual compares false and the upper neighbour's
+// residual is fma(-2^-149, 0, 0) = +0, not > 0, so s = +0 is returned.  An
+// argument known to lie in {+0} U [2^-96, FLT_MAX] therefore needs no range
+// vote (sqrt_exact): a uniform draw u in [0, 1] and 1 - u are such arguments,
+// both being 0 or at least 2^-31 (Rng::uniform returns multiples of 2^-31).
+// (Below 2^-96 and for negative arguments: vr_kernel.hpp sphere_tail.)
+__device__ __forceinline__ float sqrt_draw(float x) { return sqrt_rn(x); }
 
 // sqrtf(x) and 1.0f / sqrtf(x), bit for bit: the short sequences when every
 // active lane of the wave is in their exact range, else the IEEE expansions
