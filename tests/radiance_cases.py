@@ -19,6 +19,7 @@ import numpy as np
 
 import flag_lattice as fl
 import pyoracle as po
+import shading_cases as sh
 
 # one combination per feature class, and a mixed one (flag_lattice.name_of)
 COMBO_NAMES = ("cornell+mesh", "mesh+tex_d+tex_n+tex_s", "cornell+example", "example+view_brdf+brdf",
@@ -26,6 +27,10 @@ COMBO_NAMES = ("cornell+mesh", "mesh+tex_d+tex_n+tex_s", "cornell+example", "exa
 K_MAX = 5                          # paths per ray the shared references hold
 SAMPLES = (1, 2, 5)
 MAX_DROPPED = 0.01                 # rays whose oracle record is not finite
+# scenes of tests/shading_cases.py (odd-shaped maps, zero tangents, the example sphere with maps) and one whose NaNs
+# are the point: there nothing is dropped, a channel is equal bit for bit or NaN in both, and w is never NaN
+SHADING_NAMES = ("S_odd_C3", "D_tan0_C2N", "S_odd_C1T", "X_nrm0_tris_C3")
+SHADING_SAMPLES = (1, 2)
 TIME = fl.TIMES[0]
 
 
@@ -168,3 +173,22 @@ def reference(name, which, mesh="shallow"):
     paths.setflags(write=False)
     ok.setflags(write=False)
     return paths, ok
+
+
+@functools.lru_cache(maxsize=None)
+def shading_reference(name, which):
+    """(paths [n, 2, 4], kept [n]) of a shading case on ray set `which`; in a
+    NaN case every ray is kept."""
+    po.build()
+    o, d, s = ray_set(which)
+    paths = oracle_paths(sh.make_case(name), o, d, s, max(SHADING_SAMPLES))
+    ok = np.ones(len(paths), bool) if name in sh.NAN_CASES else kept(paths)
+    paths.setflags(write=False)
+    ok.setflags(write=False)
+    return paths, ok
+
+
+def same_or_nan_in_both(got, want) -> np.ndarray:
+    """Per record: every channel equal bit for bit, or NaN in both."""
+    got, want = np.asarray(got, np.float32), np.asarray(want, np.float32)
+    return ((u32(got) == u32(want)) | (np.isnan(got) & np.isnan(want))).all(-1)

@@ -21,6 +21,12 @@ GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 W, H = 64, 48
 FEATURE_CLASSES = ["C2D", "C3D", "C2N", "C3B", "C1T", "C4D", "CB", "C3X"]     # test_gpu_classes without C5T
 
+# the cases of tests/shading_cases.py that fit the fixture file's size cap: a shape set for each of spec_c3 and the four
+# class kernels (two for spec_c3 and the HDRI sphere kernel), two uv, four attribute and two texel cases; the others
+# are pinned to the oracle alone, like the X_ cases (tests/test_gpu_shading.py)
+SHADING_CASES = ("S_odd_C3", "S_tall_C3B", "S_tall_C2N", "S_dot_C1T", "S_odd_C4D", "U_C3", "U_C2N", "D_tan0_C3B",
+                 "D_nrm0_third_C3", "V_texels01_C3", "V_hdr_inf_C3", "S_tall_C3", "S_dot_C3X", "D_tan0_third_C2N")
+
 # name -> (family file, recipe, parameters)
 CASES = {
     "C1": ("configs", "config", dict(cfg="C1", frames=3)),
@@ -43,12 +49,14 @@ CASES = {
     "C2_near": ("views", "config", dict(cfg="C2", origin=(0.0, 0.0, 20.0), full_depth=True)),
     "C2_sbvh": ("sbvh", "sbvh", dict(cfg="C2")),
     "C3_sbvh": ("sbvh", "sbvh", dict(cfg="C3")),
+    # odd map shapes, wild uvs, zero attributes, extreme texels: recipes in tests/shading_cases.py
+    **{n: ("shading", "shading", dict(case=n)) for n in SHADING_CASES},
 }
 # cases in which no primary hit lies farther than the depth byte's range
 # (150 units), so the depth image compares on every pixel
 FULL_DEPTH = {"C4", "C3_inside", "C2_near"}
 # cases in which the reference reads vHitData::m_normal before writing it
-MAY_BE_UNDEFINED = {"C4D", "C3X"}
+MAY_BE_UNDEFINED = {"C4D", "C3X", "S_odd_C4D", "S_dot_C3X"}
 FAMILIES = sorted({v[0] for v in CASES.values()})
 
 
@@ -127,6 +135,9 @@ def make_case(name, stored=None):
         sc = scenes.make_scene(p["cfg"], w, h, knot=knot)
         sc["mesh_flat"] = None if stored is None else {k: np.array(stored[f"{name}/mesh_{k}"])
                                                        for k in ("bvh", "verts", "normals", "tangents", "uvs")}
+    elif recipe == "shading":
+        import shading_cases
+        sc = shading_cases.make_case(p["case"])
     else:
         raise ValueError(recipe)
     sc["name"] = name

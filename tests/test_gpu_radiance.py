@@ -97,6 +97,37 @@ def test_parity_on_the_deep_mesh(oracle, strict):
         r.set_strict_traversal(False)
 
 
+@pytest.mark.parametrize("strict", [False, True], ids=["culled", "strict"])
+@pytest.mark.parametrize("name", rc.SHADING_NAMES)
+def test_parity_on_shading_scenes(oracle, name, strict):
+    """Maps of odd shapes, zero tangents, the example sphere with maps, and a
+    scene with NaN normals (tests/shading_cases.py): the vr_radiance_* kernels
+    are instantiations of their own of the shading code, which saw 32 x 32 maps only."""
+    import shading_cases as sh
+    key = ("shading", name)
+    if key not in _live:
+        _live[key] = VRendererHIP(0)
+        scenes.load_into(_live[key], sh.make_case(name))
+    r = _live[key]
+    r.set_strict_traversal(strict)
+    try:
+        for which in ("A", "B"):
+            o, d, s = rc.ray_set(which)
+            paths, ok = rc.shading_reference(name, which)
+            for k in rc.SHADING_SAMPLES:
+                got, want = trace(r, o, d, s, k), rc.record_of(paths, k)
+                what = f"{name} strict={strict} set {which} samples {k}"
+                if name in sh.NAN_CASES:
+                    assert ok.all() and not np.isnan(got[:, 3]).any(), what
+                    bad = np.flatnonzero(~rc.same_or_nan_in_both(got, want))
+                    assert len(bad) == 0, f"{what}: {len(bad)} of {len(got)} records differ (first {bad[:5].tolist()}: " \
+                                          f"{got[bad[:2]].tolist()} against {want[bad[:2]].tolist()})"
+                else:
+                    same(got[ok], want[ok], what)
+    finally:
+        r.set_strict_traversal(False)
+
+
 # ---- 2. parity with the renderer, independent of the oracle -------------------------------------
 @pytest.mark.parametrize("name", rc.COMBO_NAMES)
 def test_parity_with_the_renderer(name):

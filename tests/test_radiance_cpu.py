@@ -47,6 +47,28 @@ def test_random_rays_stay_finite(oracle, native, name):
     assert len(np.unique(rc.u32(rc.record_of(paths, 5)[ok, :3]), axis=0)) > len(ok) // 4
 
 
+@pytest.mark.parametrize("name", rc.SHADING_NAMES)
+def test_shading_scenes_under_the_yardstick(oracle, native, name):
+    """The shading cases the radiance kernels are run on: within the cap on
+    dropped rays, except the NaN case, where NaN records are kept, are a
+    minority and never reach w."""
+    import shading_cases as sh
+    for which in ("A", "B"):
+        paths, ok = rc.shading_reference(name, which)
+        bad = ~np.isfinite(paths).all((1, 2))
+        if name in sh.NAN_CASES:
+            assert ok.all() and not np.isnan(paths[..., 3]).any()
+            assert not np.isinf(paths).any()                             # NaN, not infinite
+            print(f"{name} set {which}: {int(bad.sum())} of {len(bad)} rays hold a NaN")
+            assert 1 <= bad.sum() < len(bad) // 10
+        else:
+            assert bad.sum() <= rc.MAX_DROPPED * len(bad) and (ok == ~bad).all()
+        assert np.any(rc.record_of(paths, 2)[ok, :3] != 0)
+    got = np.array([[1.0, np.nan, 0.0, 2.0], [1.0, np.nan, 0.0, 2.0]], np.float32)
+    want = np.array([[1.0, -np.nan, 0.0, 2.0], [1.0, 0.5, 0.0, 2.0]], np.float32)
+    assert rc.same_or_nan_in_both(got, want).tolist() == [True, False]
+
+
 def test_record_is_the_in_order_fp32_sum():
     r = np.array([[[0.1, 0.2, 0.3, 0.5], [1e-9, 7.0, -0.0, 0.25], [3.0, 1e8, 0.7, 0.0]]], np.float32)
     c = np.float32(1.0) / np.float32(3)
