@@ -341,6 +341,89 @@ int vrhip_trace_rays(vrhip_ctx *ctx, const float *d_origins /*float[3n]*/, const
 int vrhip_trace_radiance(vrhip_ctx *ctx, const float *d_origins /*float[3n]*/, const float *d_dirs /*float[3n]*/,
                          const uint32_t *d_seeds /*uint32[2n]*/, uint32_t n_rays, uint32_t n_samples,
                          float *d_radiance /*float4[n], 16-byte aligned*/);
+/* Surface queries (no reference counterpart as a call): what does the path
+ * tracer see at the first hit of the caller's own rays?  For denoiser guide
+ * images (albedo, normal, depth), for the surface points and normals from
+ * which probes and lightmap texels spawn their vrhip_trace_radiance rays, and
+ * for picking.  The reference's intersectScene (cuda/src/PathTracer.cu:136-468)
+ * is run once along each of n_rays rays and the vHitData record it leaves
+ * (cuda/include/PathTracer.cuh:17-53), the one every bounce of trace computes
+ * and consumes, is written out with what was hit.  All arrays are device
+ * pointers on the context's device; d_hits is 16-byte aligned.
+ *   Scene: the whole scene as vrhip_render would intersect it right now --
+ *     Cornell box, the two small spheres, the example sphere, BRDF view, the
+ *     resident mesh (ignored while the example sphere is on), texture maps --
+ *     under the flag word vrhip_render computes, walked as
+ *     vrhip_set_strict_traversal says.  A mesh is not required.  The camera,
+ *     the tiling, the frame counter, the accumulation and the images play no
+ *     part and are not touched.
+ *   Ray: as vrhip_trace_radiance.  The origin is used as given; the direction
+ *     is normalised by the operation the reference applies to its camera ray
+ *     (:842-844), so t is in world units and a pixel's un-normalised camera
+ *     direction (vrhip_camera_rays) gives that pixel's camera ray.  A ray is
+ *     valid when its six floats are finite and the fp32 sum dx*dx + dy*dy +
+ *     dz*dz is finite and greater than 0.  An invalid ray is classified before
+ *     any scene test; its record is 28 zero words.
+ *   Hit: position, normal, tangent, color, specular, emission and type are
+ *     hitPoint, normal, tangent, color, spec, emission (xyz) and hitType of the
+ *     closest hit, the values bounce 0 of trace sees, quirks included: the
+ *     normal is the normal-mapped one where a normal map is loaded (and the
+ *     tangent is usable), the face normal otherwise; color is the base colour
+ *     after the diffuse map; the example sphere's texture coordinates come from
+ *     the normal the previous hit of the same call left behind (:202-204).
+ *     type: 0 specular, 1 diffuse, 2 BRDF.
+ *     kind and prim say what was hit: VRHIP_SURF_CORNELL with prim 0-5 (the
+ *     light, then the walls, in the reference's order, :113-121),
+ *     VRHIP_SURF_SMALL with prim 0-1 (:107-111), VRHIP_SURF_EXAMPLE with prim
+ *     0, VRHIP_SURF_MESH with the triangle in the caller's terms exactly as
+ *     vrhip_trace_rays defines prim, also after a refit.
+ *     bary_u, bary_v: the triangle test's barycentrics for a mesh hit, 0
+ *     otherwise.  tex_u, tex_v: the interpolated texture coordinates of a
+ *     mesh hit, (b0 * uv0 + u * uv1) + v * uv2 with b0 = 1 - u - v in fp32, 0
+ *     otherwise.  pad0 and pad1 are 0.
+ *   Miss: t = 1e20, kind = VRHIP_SURF_NONE, prim = VRHIP_RAY_MISS, every other
+ *     word 0.
+ *   Range: as vrhip_trace_radiance.  Parity with the CPU oracle is pinned for
+ *     origins at scene scale (tests/test_gpu_surface.py); the extreme-float
+ *     rules of vrhip_trace_rays are NOT applied here, and a record outside the
+ *     tested range may hold NaNs.  In the tested range a mesh hit's t, prim
+ *     and barycentrics are vrhip_trace_rays's for the normalised direction.
+ *   Cost: one ray per GPU lane, seven 16-byte stores per ray.
+ * The work runs on the context stream and the call returns when it has
+ * finished.  It touches nothing resident.  n_rays == 0: VRHIP_OK, nothing
+ * written.  VRHIP_ERR_INVALID, before any device call, for a null ctx, a null
+ * array with n_rays > 0, a misaligned d_hits, and a vrhip_create_multi context
+ * (the pointers live on one device).  VRHIP_ERR_NO_ENV in HDRI mode without an
+ * environment map, exactly where vrhip_trace_radiance returns it.
+ * Added without an ABI version change (ABI 6 gained this symbol and
+ * vrhip_camera_rays and changed no other). */
+enum { VRHIP_SURF_NONE = 0, VRHIP_SURF_CORNELL = 1, VRHIP_SURF_SMALL = 2,
+       VRHIP_SURF_EXAMPLE = 3, VRHIP_SURF_MESH = 4 };
+typedef struct vrhip_surface_hit {       /* 112 B = 7 float4, 16-byte aligned */
+    float t; uint32_t kind, prim, type;  /* type: vHitData hitType, 0 specular 1 diffuse 2 BRDF */
+    float position[3], bary_u;
+    float normal[3],   bary_v;
+    float tangent[3],  pad0;             /* 0 */
+    float color[3],    tex_u;
+    float specular[3], tex_v;
+    float emission[3], pad1;             /* 0 */
+} vrhip_surface_hit;
+int vrhip_trace_surface(vrhip_ctx *ctx, const float *d_origins /*float[3n]*/, const float *d_dirs /*float[3n]*/,
+                        uint32_t n_rays, vrhip_surface_hit *d_hits /*[n], 16-byte aligned*/);
+/* The current camera's rays as a buffer: for every pixel of the W x H image,
+ * row-major (pixel (x, y) at y * W + x, every pixel whatever the tiling), the
+ * camera origin and the UN-normalised direction (dir + cx * sx) + cy * sy of
+ * the reference's camera ray (cuda/src/PathTracer.cu:833-844, no jitter), the
+ * operand of its normalize, from the table and in the operation order the
+ * render kernels use.  vrhip_trace_surface and vrhip_trace_radiance normalise
+ * it as those kernels do and so trace the pixel's camera ray bit for bit;
+ * vrhip_trace_rays takes directions as given (its t is then in units of this
+ * direction's length).  Device pointers on the context's device, float[3 W H]
+ * each.  Runs on the context stream and returns when it has finished; closes
+ * a render-service session; touches nothing resident.  VRHIP_ERR_INVALID,
+ * before any device call, for a null ctx, a null array, and a
+ * vrhip_create_multi context. */
+int vrhip_camera_rays(vrhip_ctx *ctx, float *d_origins /*float[3*W*H]*/, float *d_dirs /*float[3*W*H]*/);
 /* replaces vRendererCuda::loadHDR (src/vRendererCuda.cpp:320-340) +
  * cu_setHDRDim: rgba float4[w*h] (or half4 with the _half variant, the
  * Imf::Rgba layout, converted on the device). */
@@ -504,7 +587,7 @@ int vrhip_set_overlap(vrhip_ctx *ctx, int mode);
  *   vrhip_gl_present, vrhip_pack_tiles/unpack_tiles, vrhip_last_kernel_ms,
  *   vrhip_kernel_stats, vrhip_debug_counters, vrhip_set_camera, vrhip_clear,
  *   every upload (vrhip_upload_mesh_device too), vrhip_refit_mesh_device,
- *   vrhip_bvh_sah_cost, vrhip_export_mesh_flat, vrhip_trace_rays, vrhip_trace_radiance, vrhip_set_stream, vrhip_set_tiling, vrhip_set_service
+ *   vrhip_bvh_sah_cost, vrhip_export_mesh_flat, vrhip_trace_rays, vrhip_trace_radiance, vrhip_trace_surface, vrhip_camera_rays, vrhip_set_stream, vrhip_set_tiling, vrhip_set_service
  *   (and its timing / budget hooks), vrhip_comm_init/destroy, vrhip_destroy,
  *   the counting renders, and a vrhip_render that does not fit the session.
  *   Calls that do NOT close it: the flag setters (Cornell box, example sphere,

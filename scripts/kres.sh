@@ -5,6 +5,9 @@
 # With a second argument `radiance`: every instantiation of the radiance query
 # kernel (vr_radiance*.hip) beside render_kernel of the same feature set:
 #   bash scripts/kres.sh variants/<name>.log radiance
+# With `surface`: every instantiation of the surface query kernel
+# (vr_surface*.hip) in the same table:
+#   bash scripts/kres.sh variants/<name>.log surface
 python3 - "$1" "$2" <<'PY'
 import re, sys
 recs, cur = {}, None
@@ -16,7 +19,8 @@ for line in open(sys.argv[1]):
     m = re.search(r"remark:\s+(VGPRs|VGPRs Spill|SGPRs Spill|ScratchSize \[bytes/lane\]|Occupancy \[waves/SIMD\]|LDS Size \[bytes/block\]): (\d+)", line)
     if m and cur is not None and m.group(1) not in cur:
         cur[m.group(1)] = int(m.group(2))
-if len(sys.argv) > 2 and sys.argv[2] == "radiance":
+if len(sys.argv) > 2 and sys.argv[2] in ("radiance", "surface"):
+    query = ("ray_radiance_kernel", "RayRadiance") if sys.argv[2] == "radiance" else ("ray_surface_kernel", "RaySurface")
     CLS, ALL = 1 << 30, 511
     sets = [("class Cornell+mesh", CLS + 253, (16, 24, 32, 64)), ("class HDRI+mesh", CLS + 252, (16, 24, 32, 64)),
             ("generic (strict)", ALL, (16, 24, 32, 64)), ("class Cornell spheres", CLS + 247, (16,)),
@@ -32,7 +36,8 @@ if len(sys.argv) > 2 and sys.argv[2] == "radiance":
     for lab, feat, stacks in sets:
         row(f"render_kernel<16> {lab}", f"_ZN2vr13render_kernelILi16ELb0ELj{feat}EEEvNS_12RenderParamsE")
         for st in stacks:
-            row(f"  ray_radiance_kernel<{st}> {lab}", f"_ZN2vr19ray_radiance_kernelILi{st}ELj{feat}EEEvNS_12RenderParamsENS_11RayRadianceE")
+            row(f"  {query[0]}<{st}> {lab}",
+                f"_ZN2vr{len(query[0])}{query[0]}ILi{st}ELj{feat}EEEvNS_12RenderParamsENS_{len(query[1])}{query[1]}E")
     sys.exit(0)
 E, INL, SML, SVC, SPA = 2147483648, 8192, 16384, 32768, 65536
 C2, C3, C5 = E + 9, E + 232, E + 8

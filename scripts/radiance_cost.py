@@ -42,21 +42,16 @@ from vrenderer_pathtracer_amd import VRendererHIP, scenes  # noqa: E402
 SAMPLES = (2, 32)
 
 
-def camera_rays(sc, n, dev):
-    """PathTracer.cu:833-843 in float32 on the device: (origins, un-normalised dirs, seeds (x, y * time)) of
-    the first n pixels, row-major, wrapped."""
-    W, H, cam = sc["width"], sc["height"], sc["camera"]
-    f = lambda v: torch.tensor(v, dtype=torch.float32, device=dev)          # noqa: E731
-    sx = np.float32(cam["fov_scale"]) * np.float32(W) / np.float32(H)
-    cx, cy = f(cam["right"]) * float(sx), f(cam["up"]) * float(np.float32(cam["fov_scale"]))
-    i = torch.arange(n, device=dev) % (W * H)
+def camera_rays(r, sc, n):
+    """The renderer's own camera rays (cameraRays(): the un-normalised directions, as the call takes them) and the
+    seeds (x, y * time) render gives a pixel: the first n pixels, row-major, wrapped."""
+    o, d = r.cameraRays()
+    W = sc["width"]
+    i = torch.arange(n, device=o.device) % o.shape[0]
     x, y = i % W, i // W
-    px = ((0.25 + x.double()) / W - 0.5).float()[:, None]
-    py = ((0.25 + y.double()) / H - 0.5).float()[:, None]
-    d = f(cam["dir"])[None, :] + cx[None, :] * px + cy[None, :] * py
     seeds = torch.stack([x, (y * int(sc["time"])) & 0xFFFFFFFF], 1)
     seeds = torch.where(seeds >= 2**31, seeds - 2**32, seeds).to(torch.int32)
-    return f(cam["origin"])[None, :].expand(n, 3).contiguous(), d.contiguous(), seeds.contiguous()
+    return o[i].contiguous(), d[i].contiguous(), seeds.contiguous()
 
 
 def random_rays(lo, hi, n, dev, seed=7):
@@ -95,7 +90,7 @@ def measure(cfg, n_rays, bench):
     verts = torch.from_numpy(np.ascontiguousarray(sc["mesh_flat"]["verts"][:, :3])).to(dev)
     out = {"scene": cfg, "n_slots": int(verts.shape[0]), "depth": r.bvh_info()[0], "walk": "culled", "n_rays": n_rays,
            "resolution": [sc["width"], sc["height"]]}
-    sets = {"camera": camera_rays(sc, n_rays, dev),
+    sets = {"camera": camera_rays(r, sc, n_rays),
             "random": random_rays(verts.min(0).values, verts.max(0).values, n_rays, dev)}
     for name, (o, d, s) in sets.items():
         for k in SAMPLES:

@@ -39,19 +39,13 @@ import torch  # noqa: E402
 from vrenderer_pathtracer_amd import VRendererHIP, scenes  # noqa: E402
 
 
-def camera_rays(sc, n, dev):
-    """PathTracer.cu:833-844 in float32 on the device: (origins, dirs) of the first n pixels, row-major, wrapped."""
-    W, H, cam = sc["width"], sc["height"], sc["camera"]
-    f = lambda v: torch.tensor(v, dtype=torch.float32, device=dev)          # noqa: E731
-    sx = np.float32(cam["fov_scale"]) * np.float32(W) / np.float32(H)
-    cx, cy = f(cam["right"]) * float(sx), f(cam["up"]) * float(np.float32(cam["fov_scale"]))
-    i = torch.arange(n, device=dev) % (W * H)
-    x, y = (i % W).double(), (i // W).double()
-    px = ((0.25 + x) / W - 0.5).float()[:, None]
-    py = ((0.25 + y) / H - 0.5).float()[:, None]
-    d = f(cam["dir"])[None, :] + cx[None, :] * px + cy[None, :] * py
+def camera_rays(r, n):
+    """The renderer's own camera rays (cameraRays(): cuda/src/PathTracer.cu:833-844), normalised as the camera ray is:
+    (origins, dirs) of the first n pixels, row-major, wrapped."""
+    o, d = r.cameraRays()
+    i = torch.arange(n, device=o.device) % o.shape[0]
     d = d / d.norm(dim=1, keepdim=True)
-    return f(cam["origin"])[None, :].expand(n, 3).contiguous(), d.contiguous()
+    return o[i].contiguous(), d[i].contiguous()
 
 
 def random_rays(lo, hi, n, dev, seed=7):
@@ -93,7 +87,7 @@ def measure(cfg, nu, nv, leaf, builder, n_rays, frames):
     stream = torch.cuda.ExternalStream(r.get_stream(), device=dev)
     out = {"scene": cfg, "knot": [nu, nv], "n_tris": int(len(mesh["tris"])), "max_leaf_tris": leaf, "builder": builder,
            "depth": r.bvh_info()[0], "walk": "culled", "n_rays": n_rays, "resolution": [sc["width"], sc["height"]]}
-    sets = {"coherent": camera_rays(sc, n_rays, dev),
+    sets = {"coherent": camera_rays(r, n_rays),
             "incoherent": random_rays(pos.min(0).values, pos.max(0).values, n_rays, dev)}
     for name, (o, d) in sets.items():
         for any_hit in (False, True):

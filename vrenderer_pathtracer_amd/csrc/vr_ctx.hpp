@@ -379,6 +379,21 @@ inline void scene_params(const vrhip_ctx* c, vr::RenderParams& p)
     p.brdf = c->brdf;
 }
 
+// The camera half of a launch's parameters: what camera_ray reads.
+// vrhip_render (build_params) and vrhip_camera_rays take the same camera
+// through it.
+inline void camera_params(const vrhip_ctx* c, vr::RenderParams& p)
+{
+    p.cam_o = vr4{ c->cam_o[0], c->cam_o[1], c->cam_o[2], 0.f };
+    p.cam_d = vr4{ c->cam_d[0], c->cam_d[1], c->cam_d[2], 0.f };
+    // PathTracer.cu:833-836 in the same fp32 operation order
+    const float sx = c->fov_scale * (float)c->W / (float)c->H;
+    p.cx = vr4{ sx * c->cam_right[0], sx * c->cam_right[1], sx * c->cam_right[2], 0.f };
+    p.cy = vr4{ c->fov_scale * c->cam_up[0], c->fov_scale * c->cam_up[1], c->fov_scale * c->cam_up[2], 0.f };
+    p.W = c->W; p.H = c->H;
+    p.cam_sxy = c->cam_sxy;
+}
+
 // traversal stack entries for a tree of this depth (the walk needs depth + 1),
 // rounded up to a size the kernels are built for
 inline int mesh_stack_entries(uint32_t depth) { return depth <= 15 ? 16 : depth <= 23 ? 24 : depth <= 30 ? 32 : 64; }

@@ -1,13 +1,17 @@
 // vrhip_query.cpp -- the queries along the caller's own rays on the device
 // (include/vrhip.h): where a ray hits the resident mesh (vrhip_trace_rays,
 // vr_rayquery.hip) and what light arrives along it (vrhip_trace_radiance,
-// vr_radiance.hip).  Both read the scene only: the accumulation, the images
-// and the frame counter stay as they are.
+// vr_radiance.hip), what the path tracer sees at its first hit
+// (vrhip_trace_surface, vr_surface.hip), and the current camera's rays to feed
+// them (vrhip_camera_rays).  All read the scene only: the accumulation, the
+// images and the frame counter stay as they are.
+#include <cstddef>
 #include <cstring>
 
 #include "vr_ctx.hpp"
 #include "vr_radiance.hpp"
 #include "vr_rayquery.hpp"
+#include "vr_surface.hpp"
 
 // Ray queries against the resident mesh: the path kernels' traversal fed from
 // the caller's ray buffer.
@@ -65,6 +69,58 @@ int vrhip_trace_radiance(vrhip_ctx* c, const float* d_origins, const float* d_di
     (void)hipGetLastError();            // the launch below reports its own error only
     const int e = vr::launch_ray_radiance(p, q, mesh_stack_entries(c->mesh.a.depth), c->cu_count, c->stream);
     if (e) return fail(VRHIP_ERR_HIP, std::string("radiance query: ") + hipGetErrorString((hipError_t)e));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return svc_verify(c);
+}
+
+// The surface at the first hit of the caller's rays: vrhip_trace_radiance's
+// scene, rays and order of checks, intersect_scene and fill_hit run once per
+// ray and the record written out.
+static_assert(sizeof(vrhip_surface_hit) == 112 && sizeof(vr::SurfaceHit) == 112, "seven 16-B rows per ray");
+static_assert(offsetof(vrhip_surface_hit, position) == 16 && offsetof(vrhip_surface_hit, normal) == 32 &&
+                  offsetof(vrhip_surface_hit, tangent) == 48 && offsetof(vrhip_surface_hit, color) == 64 &&
+                  offsetof(vrhip_surface_hit, specular) == 80 && offsetof(vrhip_surface_hit, emission) == 96,
+              "the rows of vrhip_surface_hit");
+static_assert(VRHIP_SURF_NONE == (int)vr::kSurfNone && VRHIP_SURF_CORNELL == (int)vr::kSurfCornell &&
+                  VRHIP_SURF_SMALL == (int)vr::kSurfSmall && VRHIP_SURF_EXAMPLE == (int)vr::kSurfExample &&
+                  VRHIP_SURF_MESH == (int)vr::kSurfMesh, "SurfaceHit::kind");
+int vrhip_trace_surface(vrhip_ctx* c, const float* d_origins, const float* d_dirs, uint32_t n_rays,
+                        vrhip_surface_hit* d_hits)
+{
+    if (!c) return fail(VRHIP_ERR_INVALID, "null ctx");
+    if (n_rays > 0 && (!d_origins || !d_dirs || !d_hits)) return fail(VRHIP_ERR_INVALID, "null ray or hit array");
+    if (((uintptr_t)d_hits & 15u) != 0u) return fail(VRHIP_ERR_INVALID, "d_hits is not 16-byte aligned");
+    if (!c->group.empty()) return refuse_multi(c, "vrhip_trace_surface");
+    if (n_rays == 0) return VRHIP_OK;
+    if (!c->cornell && !c->hdr)
+        return fail(VRHIP_ERR_NO_ENV, "HDRI mode needs an environment map (vrhip_upload_hdr)");
+    int rc = set_device(c); if (rc) return rc;
+    if ((rc = svc_close(c)) != VRHIP_OK) return rc;
+    vr::RenderParams p;
+    std::memset(&p, 0, sizeof(p));
+    scene_params(c, p);
+    const vr::RaySurface q{ d_origins, d_dirs, n_rays, c->mesh.a.prim_id, (vr::SurfaceHit*)d_hits };
+    (void)hipGetLastError();            // the launch below reports its own error only
+    const int e = vr::launch_ray_surface(p, q, mesh_stack_entries(c->mesh.a.depth), c->cu_count, c->stream);
+    if (e) return fail(VRHIP_ERR_HIP, std::string("surface query: ") + hipGetErrorString((hipError_t)e));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return svc_verify(c);
+}
+
+// The current camera's rays, one per pixel of the whole image, row-major.
+int vrhip_camera_rays(vrhip_ctx* c, float* d_origins, float* d_dirs)
+{
+    if (!c) return fail(VRHIP_ERR_INVALID, "null ctx");
+    if (!d_origins || !d_dirs) return fail(VRHIP_ERR_INVALID, "null origin or direction array");
+    if (!c->group.empty()) return refuse_multi(c, "vrhip_camera_rays");
+    int rc = set_device(c); if (rc) return rc;
+    if ((rc = svc_close(c)) != VRHIP_OK) return rc;
+    vr::RenderParams p;
+    std::memset(&p, 0, sizeof(p));
+    camera_params(c, p);
+    (void)hipGetLastError();            // the launch below reports its own error only
+    const int e = vr::launch_camera_rays(p, d_origins, d_dirs, c->stream);
+    if (e) return fail(VRHIP_ERR_HIP, std::string("camera rays: ") + hipGetErrorString((hipError_t)e));
     HIP_TRY(hipStreamSynchronize(c->stream));
     return svc_verify(c);
 }

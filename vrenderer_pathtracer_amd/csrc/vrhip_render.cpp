@@ -269,14 +269,7 @@ static void build_params(const vrhip_ctx* c, RenderCall& q)
 {
     vr::RenderParams& p = q.p;
     std::memset(&p, 0, sizeof(p));
-    p.cam_o = vr4{ c->cam_o[0], c->cam_o[1], c->cam_o[2], 0.f };
-    p.cam_d = vr4{ c->cam_d[0], c->cam_d[1], c->cam_d[2], 0.f };
-    // PathTracer.cu:833-836 in the same fp32 operation order
-    const float sx = c->fov_scale * (float)c->W / (float)c->H;
-    p.cx = vr4{ sx * c->cam_right[0], sx * c->cam_right[1], sx * c->cam_right[2], 0.f };
-    p.cy = vr4{ c->fov_scale * c->cam_up[0], c->fov_scale * c->cam_up[1], c->fov_scale * c->cam_up[2], 0.f };
-    p.W = c->W; p.H = c->H;
-    p.cam_sxy = c->cam_sxy;
+    camera_params(c, p);
     p.tone_t = c->tone_t;
     p.wr = (c->W / 16u) * 16u; p.hr = rendered_rows(c);
     scene_params(c, p);

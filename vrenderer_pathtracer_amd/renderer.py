@@ -95,6 +95,7 @@ def flat_sah_cost(flat: dict) -> float:
 
 RAY_MISS = 0xFFFFFFFF                    # VRHIP_RAY_MISS
 RAYS_CLOSEST, RAYS_ANY = 0, 1           # vrhip_trace_rays modes
+SURF_NONE, SURF_CORNELL, SURF_SMALL, SURF_EXAMPLE, SURF_MESH = range(5)   # vrhip_surface_hit kind (VRHIP_SURF_*)
 
 
 def _unpack_hits(rec, xp):
@@ -418,6 +419,62 @@ class VRendererHIP:
         check(self._lib.vrhip_trace_radiance(self._ctx, p_o, p_d, p_s, n, int(samples),
                                              ctypes.c_void_p(out.data_ptr())), "vrhip_trace_radiance")
         return out
+
+    def traceSurface(self, origins, dirs) -> dict:
+        """What does the path tracer see at the first hit of these rays
+        (vrhip_trace_surface)?  The whole scene as render() would intersect it
+        now: the Cornell box, the small spheres, the example sphere and the
+        mesh, with the maps applied.  origins, dirs: (N,3) float32 torch
+        tensors on the renderer's GPU, contiguous; directions are normalised
+        by the library, so t is in world units.  Returns views of one (N,28)
+        float32 device tensor (the dict's "record"): t (N,) float32; kind,
+        prim, type (N,) int32 (kind: SURF_NONE .. SURF_MESH; prim: the sphere's
+        index or the triangle as traceRays names it, -1 for a miss; type: 0
+        specular, 1 diffuse, 2 BRDF); position, normal, tangent, color,
+        specular, emission (N,3); bary and uv (N,2), a mesh hit's barycentrics
+        and interpolated texture coordinates.  A miss has t = 1e20 and kind 0;
+        a ray with a non-finite float or a direction of zero or overflowing
+        length gives 28 zero words.  ValueError for a wrong device, dtype,
+        shape or layout.  Synchronises torch's current stream first; the query
+        runs on the renderer's own stream and has finished on return."""
+        import torch
+        self._need_ctx()
+        dev = self._torch_device()
+        ptr = self._tensor_ptr
+        p_o = ptr("origins", origins, 3, (torch.float32,))
+        if p_o is None:
+            raise ValueError("origins and dirs are required")
+        n = int(origins.shape[0])
+        p_d = ptr("dirs", dirs, 3, (torch.float32,), n)
+        if p_d is None:
+            raise ValueError("origins and dirs are required")
+        rec = torch.empty((n, 28), dtype=torch.float32, device=f"cuda:{dev}")
+        torch.cuda.current_stream(dev).synchronize()
+        check(self._lib.vrhip_trace_surface(self._ctx, p_o, p_d, n, ctypes.c_void_p(rec.data_ptr())),
+              "vrhip_trace_surface")
+        words = rec.view(torch.int32)
+        return {"record": rec, "t": rec[:, 0], "kind": words[:, 1], "prim": words[:, 2], "type": words[:, 3],
+                "position": rec[:, 4:7], "normal": rec[:, 8:11], "tangent": rec[:, 12:15], "color": rec[:, 16:19],
+                "specular": rec[:, 20:23], "emission": rec[:, 24:27], "bary": rec[:, 7:12:4], "uv": rec[:, 19:24:4]}
+
+    def cameraRays(self):
+        """The current camera's rays (vrhip_camera_rays): (origins, dirs), each
+        an (H*W, 3) float32 device tensor, pixel (x, y) in row y * W + x.  The
+        directions are un-normalised, the operand of the camera ray's
+        normalisation: traceSurface and traceRadiance normalise them as the
+        render kernels do and so trace each pixel's own camera ray."""
+        import torch
+        self._need_ctx()
+        if self._camera is not None and self._camera.is_dirty():
+            self.updateCamera()
+        dev = self._torch_device()
+        n = int(self.width) * int(self.height)
+        o = torch.empty((n, 3), dtype=torch.float32, device=f"cuda:{dev}")
+        d = torch.empty((n, 3), dtype=torch.float32, device=f"cuda:{dev}")
+        torch.cuda.current_stream(dev).synchronize()
+        check(self._lib.vrhip_camera_rays(self._ctx, ctypes.c_void_p(o.data_ptr()), ctypes.c_void_p(d.data_ptr())),
+              "vrhip_camera_rays")
+        return o, d
 
     def _torch_device(self) -> int:
         """The GPU index device tensors must live on (a group's first device)."""
