@@ -1700,6 +1700,27 @@ constexpr bool retire_first() {
     return (FEAT & (F_EXACT | F_CLASS)) != 0u && (FEAT & F_CORNELL) != 0u && (FEAT & F_MESH) != 0u &&
            (FEAT & (F_INLINE_PRIM | F_SMALL)) == 0u;
 }
+// Phase priority (s_setprio) in the retire_first kernels: VR_PRIO_TRAV on
+// entry to the traversal loop, VR_PRIO_SHADE for the retire / refill / shade /
+// set-up sequence that follows it, 0 around a wait on the session's ring and
+// at kernel exit.  VALU issue goes by priority, then age: at equal priority a
+// traversal wave whose node load has returned (about 55 VALU per visit, then
+// the next dependent load) queues behind the other waves' shading bursts of
+// several hundred VALU; one step up lets it issue its next load first.
+// Measured (C2, 16-frame steps, three alternations, same hash,
+// profiles/phase_prio/): 1 / 0 +2.6 %, 2 / 0 +2.5 %, the reverse 0 / 2
+// -2.0 %, 2 inside trav_iter's leaf loop only -1.7 %.  VR_PHASE_PRIO 0: off.
+#ifndef VR_PHASE_PRIO
+#define VR_PHASE_PRIO 1
+#endif
+#ifndef VR_PRIO_TRAV
+#define VR_PRIO_TRAV 1
+#endif
+#ifndef VR_PRIO_SHADE
+#define VR_PRIO_SHADE 0
+#endif
+template <uint32_t FEAT>
+constexpr bool phase_prio() { return VR_PHASE_PRIO != 0 && retire_first<FEAT>(); }
 enum LaneState : int { LS_SETUP = 0, LS_TRAV = 1, LS_SHADE = 2, LS_DONE = 3, LS_CAMERA = 4, LS_HELP = 5, LS_HELPDONE = 6 };
 
 // Helpers (the launch's drain).  Once the work queues are empty, a wave's
@@ -2138,6 +2159,7 @@ __device__ __forceinline__ void wave_body(const RenderParams& p, const Lds& L)
             }
         }
         if (HAS(F_MESH)) {
+            if constexpr (phase_prio<FEAT>()) __builtin_amdgcn_s_setprio(VR_PRIO_TRAV);
             for (;;) {
                 const int n_trav = __popcll(__ballot(state == LS_TRAV || state == LS_HELP));
                 if constexpr (RETIRE) {
@@ -2148,6 +2170,7 @@ __device__ __forceinline__ void wave_body(const RenderParams& p, const Lds& L)
                                        (cur_sub == ~0u && n_shade > 0 &&
                                         n_shade * VR_DRAIN_SHADE_NUM >= n_trav * VR_DRAIN_SHADE_DEN);
                     if (leave) {
+                        if constexpr (phase_prio<FEAT>()) __builtin_amdgcn_s_setprio(VR_PRIO_SHADE);
                         const bool rt = state == LS_SHADE && path_ends_short(hr, ps);
                         if (rt) {
                             vr4 out;
@@ -2248,6 +2271,7 @@ __device__ __forceinline__ void wave_body(const RenderParams& p, const Lds& L)
         if constexpr (!RETIRE) refill(ended);
         if (__ballot(state != LS_DONE) == 0ull) break;
     }
+    if constexpr (phase_prio<FEAT>()) __builtin_amdgcn_s_setprio(0);
     if (CNT) flush_counts(p, cnt, lane, true);
 }
 
@@ -2518,7 +2542,16 @@ __device__ __forceinline__ void service_body(const RenderParams& p, const Lds& L
                 else next += need;
             }
             if (__ballot(state != LS_DONE) != 0ull) return true;
-            if (ring == DONE || !wait_chunk()) return false;
+            if constexpr (phase_prio<FEAT>() && VR_PRIO_SHADE != 0) {
+                // an idle wave waits at priority 0 whatever the shading priority
+                if (ring == DONE) return false;
+                __builtin_amdgcn_s_setprio(0);
+                const bool got = wait_chunk();
+                __builtin_amdgcn_s_setprio(VR_PRIO_SHADE);
+                if (!got) return false;
+            } else {
+                if (ring == DONE || !wait_chunk()) return false;
+            }
             next = 0u;
             take = true;
         }
@@ -2536,6 +2569,7 @@ __device__ __forceinline__ void service_body(const RenderParams& p, const Lds& L
         }
         bool over = false;
         if (HAS(F_MESH)) {
+            if constexpr (phase_prio<FEAT>()) __builtin_amdgcn_s_setprio(VR_PRIO_TRAV);
             for (;;) {
                 const int n_trav = __popcll(__ballot(state == LS_TRAV));
                 if constexpr (RETIRE) {
@@ -2551,6 +2585,7 @@ __device__ __forceinline__ void service_body(const RenderParams& p, const Lds& L
                                        (cur_sub == ~0u && n_shade > 0 &&
                                         n_shade * VR_DRAIN_SHADE_NUM >= n_trav * VR_DRAIN_SHADE_DEN);
                     if (leave) {
+                        if constexpr (phase_prio<FEAT>()) __builtin_amdgcn_s_setprio(VR_PRIO_SHADE);
                         const bool rt = state == LS_SHADE && path_ends_short(hr, ps);
                         if (rt) {
                             vr4 out;
@@ -2606,6 +2641,7 @@ __device__ __forceinline__ void service_body(const RenderParams& p, const Lds& L
             if (!refill(ended)) break;
         }
     }
+    if constexpr (phase_prio<FEAT>()) __builtin_amdgcn_s_setprio(0);
 }
 
 // the service kernel runs at the scene kernel's residency and node cache (path_waves, path_cache_nodes)
