@@ -424,6 +424,70 @@ int vrhip_trace_surface(vrhip_ctx *ctx, const float *d_origins /*float[3n]*/, co
  * before any device call, for a null ctx, a null array, and a
  * vrhip_create_multi context. */
 int vrhip_camera_rays(vrhip_ctx *ctx, float *d_origins /*float[3*W*H]*/, float *d_dirs /*float[3*W*H]*/);
+/* Radiance from the caller's surface records (no reference counterpart as a
+ * call): what would the renderer show for this surface, seen from this
+ * direction?  For lightmap texels and irradiance probes, whose points and
+ * normals come from a UV unwrap or a probe grid and were never reached by a
+ * ray, and for relighting the records of vrhip_trace_surface with other
+ * materials.  The reference's trace (cuda/src/PathTracer.cu:597-770) is run
+ * with the result of bounce 0's intersectScene given by the caller: a miss
+ * takes :631-652 along the direction, a hit takes :664-764 with the record as
+ * vHitData; bounces 1 to 3 are the render's own.  One float4 per record is
+ * written.  All arrays are device pointers on the context's device; d_hits and
+ * d_radiance are 16-byte aligned.
+ *   Scene: as vrhip_trace_radiance -- the whole scene as vrhip_render would
+ *     trace it right now, under its flag word, walked as
+ *     vrhip_set_strict_traversal says.  A mesh is not required.
+ *   Record: kind is read only as 0 = miss, 1..4 = hit.  Of a hit position,
+ *     normal, tangent, color, specular, emission (xyz, w taken as 0) and type
+ *     are read; t, prim, the barycentrics, tex_u, tex_v and the pads are not.
+ *     The normal is used as given and is NOT normalised (the reference uses a
+ *     unit hit.normal; pass one).  Non-finite values and zero vectors in a
+ *     record propagate as the render's arithmetic propagates them: a zero
+ *     normal gives NaN radiance.  d_dirs[3i..3i+2] is the incoming direction
+ *     of record i (the ray that arrives at the surface, pointing at it),
+ *     normalised by the operation the other queries use.  A record is invalid
+ *     when a float of its direction is not finite or the fp32 sum dx*dx +
+ *     dy*dy + dz*dz is not finite and greater than 0, when kind > 4, or when it
+ *     is a hit with type > 2.  An invalid record is classified before any scene
+ *     work; its result is {0, 0, 0, 0}.
+ *   Paths: as vrhip_trace_radiance -- record i runs n_samples paths one after
+ *     the other on the seed stream (d_seeds[2i], d_seeds[2i+1]).
+ *     1 <= n_samples <= 4096.
+ *   Result: rgb = ((0 + r_0 * c) + r_1 * c) + ... in path order with
+ *     c = 1.f / (float)n_samples, every product and sum rounded in fp32.
+ *     w = 0: without a camera origin there is no depth term.
+ *   Consequences:
+ *     1. vrhip_trace_surface(o, d) followed by this call with the same d,
+ *        seeds and n_samples gives the rgb of vrhip_trace_radiance(o, d, ...)
+ *        bit for bit, in both traversal modes.
+ *     2. A record with type = 1, specular.x = 0 and emission = 0 does not
+ *        depend on its direction (the Fresnel draw is still taken and
+ *        discarded, :678-722).  With color = (1, 1, 1) it is what a lightmap
+ *        texel or an irradiance probe stores: the reference's diffuse estimate
+ *        at that point and normal.  It is not an irradiance in W/m^2: it
+ *        carries the reference's own weight 2 * cos on a cosine-distributed
+ *        sample (for a uniform incoming radiance L it converges to
+ *        2 * E[cos] * L = 4/3 L, where L is the physical answer).  The factor
+ *        is the reference's and is not corrected.
+ *     3. Range: as vrhip_trace_radiance.  Parity with the CPU oracle is pinned
+ *        for points at scene scale (tests/test_gpu_shade.py); there is no
+ *        extreme-float walk.
+ *   Cost: one record per GPU lane, as vrhip_trace_radiance: a lane whose paths
+ *     end early idles until the slowest of its 64 neighbours has finished.
+ *     (Lanes that take the next record at once were built and measured and
+ *     did not win on the Cornell box)
+ * The work runs on the context stream and the call returns when it has
+ * finished.  It closes a render-service session and touches nothing resident.
+ * n_hits == 0: VRHIP_OK, nothing written.  VRHIP_ERR_INVALID, before any device
+ * call, for a null ctx, a null array with n_hits > 0, a misaligned d_hits or
+ * d_radiance, n_samples outside [1, 4096], and a vrhip_create_multi context.
+ * VRHIP_ERR_NO_ENV in HDRI mode without an environment map, exactly where
+ * vrhip_trace_radiance returns it.  Added without an ABI version change (ABI 6
+ * gained this symbol and changed no other). */
+int vrhip_shade_surface(vrhip_ctx *ctx, const vrhip_surface_hit *d_hits /*[n], 16-byte aligned*/,
+                        const float *d_dirs /*float[3n]*/, const uint32_t *d_seeds /*uint32[2n]*/,
+                        uint32_t n_hits, uint32_t n_samples, float *d_radiance /*float4[n], 16-byte aligned*/);
 /* replaces vRendererCuda::loadHDR (src/vRendererCuda.cpp:320-340) +
  * cu_setHDRDim: rgba float4[w*h] (or half4 with the _half variant, the
  * Imf::Rgba layout, converted on the device). */
@@ -587,7 +651,7 @@ int vrhip_set_overlap(vrhip_ctx *ctx, int mode);
  *   vrhip_gl_present, vrhip_pack_tiles/unpack_tiles, vrhip_last_kernel_ms,
  *   vrhip_kernel_stats, vrhip_debug_counters, vrhip_set_camera, vrhip_clear,
  *   every upload (vrhip_upload_mesh_device too), vrhip_refit_mesh_device,
- *   vrhip_bvh_sah_cost, vrhip_export_mesh_flat, vrhip_trace_rays, vrhip_trace_radiance, vrhip_trace_surface, vrhip_camera_rays, vrhip_set_stream, vrhip_set_tiling, vrhip_set_service
+ *   vrhip_bvh_sah_cost, vrhip_export_mesh_flat, vrhip_trace_rays, vrhip_trace_radiance, vrhip_trace_surface, vrhip_shade_surface, vrhip_camera_rays, vrhip_set_stream, vrhip_set_tiling, vrhip_set_service
  *   (and its timing / budget hooks), vrhip_comm_init/destroy, vrhip_destroy,
  *   the counting renders, and a vrhip_render that does not fit the session.
  *   Calls that do NOT close it: the flag setters (Cornell box, example sphere,

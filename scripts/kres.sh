@@ -8,6 +8,9 @@
 # With `surface`: every instantiation of the surface query kernel
 # (vr_surface*.hip) in the same table:
 #   bash scripts/kres.sh variants/<name>.log surface
+# With `shade`: every instantiation of the surface-record radiance kernel
+# (vr_shade*.hip) in the same table:
+#   bash scripts/kres.sh variants/<name>.log shade
 python3 - "$1" "$2" <<'PY'
 import re, sys
 recs, cur = {}, None
@@ -19,8 +22,10 @@ for line in open(sys.argv[1]):
     m = re.search(r"remark:\s+(VGPRs|VGPRs Spill|SGPRs Spill|ScratchSize \[bytes/lane\]|Occupancy \[waves/SIMD\]|LDS Size \[bytes/block\]): (\d+)", line)
     if m and cur is not None and m.group(1) not in cur:
         cur[m.group(1)] = int(m.group(2))
-if len(sys.argv) > 2 and sys.argv[2] in ("radiance", "surface"):
-    query = ("ray_radiance_kernel", "RayRadiance") if sys.argv[2] == "radiance" else ("ray_surface_kernel", "RaySurface")
+QUERIES = {"radiance": ("ray_radiance_kernel", "RayRadiance"), "surface": ("ray_surface_kernel", "RaySurface"),
+           "shade": ("surface_shade_kernel", "SurfaceShade")}
+if len(sys.argv) > 2 and sys.argv[2] in QUERIES:
+    query = QUERIES[sys.argv[2]]
     CLS, ALL = 1 << 30, 511
     sets = [("class Cornell+mesh", CLS + 253, (16, 24, 32, 64)), ("class HDRI+mesh", CLS + 252, (16, 24, 32, 64)),
             ("generic (strict)", ALL, (16, 24, 32, 64)), ("class Cornell spheres", CLS + 247, (16,)),

@@ -2,8 +2,9 @@
 // (include/vrhip.h): where a ray hits the resident mesh (vrhip_trace_rays,
 // vr_rayquery.hip) and what light arrives along it (vrhip_trace_radiance,
 // vr_radiance.hip), what the path tracer sees at its first hit
-// (vrhip_trace_surface, vr_surface.hip), and the current camera's rays to feed
-// them (vrhip_camera_rays).  All read the scene only: the accumulation, the
+// (vrhip_trace_surface, vr_surface.hip), what light leaves a surface record the
+// caller supplies (vrhip_shade_surface, vr_shade.hip), and the current camera's
+// rays to feed them (vrhip_camera_rays).  All read the scene only: the accumulation, the
 // images and the frame counter stay as they are.
 #include <cstddef>
 #include <cstring>
@@ -11,6 +12,7 @@
 #include "vr_ctx.hpp"
 #include "vr_radiance.hpp"
 #include "vr_rayquery.hpp"
+#include "vr_shade.hpp"
 #include "vr_surface.hpp"
 
 // Ray queries against the resident mesh: the path kernels' traversal fed from
@@ -103,6 +105,46 @@ int vrhip_trace_surface(vrhip_ctx* c, const float* d_origins, const float* d_dir
     (void)hipGetLastError();            // the launch below reports its own error only
     const int e = vr::launch_ray_surface(p, q, mesh_stack_entries(c->mesh.a.depth), c->cu_count, c->stream);
     if (e) return fail(VRHIP_ERR_HIP, std::string("surface query: ") + hipGetErrorString((hipError_t)e));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return svc_verify(c);
+}
+
+// Radiance from the caller's surface records: vrhip_trace_radiance's scene,
+// session handling and order of checks, trace entered at bounce 0's shading
+// with the record as its hit.  The kernel reads a record as seven 16-byte
+// rows and takes kind and type from the first.
+static_assert(offsetof(vrhip_surface_hit, kind) == 4 && offsetof(vrhip_surface_hit, type) == 12 &&
+                  offsetof(vr::SurfaceHit, kind) == 4 && offsetof(vr::SurfaceHit, type) == 12 &&
+                  offsetof(vr::SurfaceHit, position) == 16 && offsetof(vr::SurfaceHit, normal) == 32 &&
+                  offsetof(vr::SurfaceHit, tangent) == 48 && offsetof(vr::SurfaceHit, color) == 64 &&
+                  offsetof(vr::SurfaceHit, specular) == 80 && offsetof(vr::SurfaceHit, emission) == 96 &&
+                  alignof(vr::SurfaceHit) == 16,
+              "the rows surface_shade_kernel loads");
+static_assert(vr::kShadeMaxSamples == vr::kRadianceMaxSamples, "one bound on the paths per call");
+int vrhip_shade_surface(vrhip_ctx* c, const vrhip_surface_hit* d_hits, const float* d_dirs, const uint32_t* d_seeds,
+                        uint32_t n_hits, uint32_t n_samples, float* d_radiance)
+{
+    if (!c) return fail(VRHIP_ERR_INVALID, "null ctx");
+    if (n_hits > 0 && (!d_hits || !d_dirs || !d_seeds || !d_radiance))
+        return fail(VRHIP_ERR_INVALID, "null record, direction, seed or radiance array");
+    if (((uintptr_t)d_hits & 15u) != 0u) return fail(VRHIP_ERR_INVALID, "d_hits is not 16-byte aligned");
+    if (((uintptr_t)d_radiance & 15u) != 0u) return fail(VRHIP_ERR_INVALID, "d_radiance is not 16-byte aligned");
+    if (n_samples < 1u || n_samples > vr::kShadeMaxSamples)
+        return fail(VRHIP_ERR_INVALID, "n_samples is " + std::to_string(n_samples) + " (1 to " +
+                                           std::to_string(vr::kShadeMaxSamples) + ")");
+    if (!c->group.empty()) return refuse_multi(c, "vrhip_shade_surface");
+    if (n_hits == 0) return VRHIP_OK;
+    if (!c->cornell && !c->hdr)
+        return fail(VRHIP_ERR_NO_ENV, "HDRI mode needs an environment map (vrhip_upload_hdr)");
+    int rc = set_device(c); if (rc) return rc;
+    if ((rc = svc_close(c)) != VRHIP_OK) return rc;
+    vr::RenderParams p;
+    std::memset(&p, 0, sizeof(p));
+    scene_params(c, p);
+    const vr::SurfaceShade q{ (const vr::SurfaceHit*)d_hits, d_dirs, d_seeds, n_hits, n_samples, (vr4*)d_radiance };
+    (void)hipGetLastError();            // the launch below reports its own error only
+    const int e = vr::launch_surface_shade(p, q, mesh_stack_entries(c->mesh.a.depth), c->cu_count, c->stream);
+    if (e) return fail(VRHIP_ERR_HIP, std::string("surface shading: ") + hipGetErrorString((hipError_t)e));
     HIP_TRY(hipStreamSynchronize(c->stream));
     return svc_verify(c);
 }

@@ -457,6 +457,85 @@ class VRendererHIP:
                 "position": rec[:, 4:7], "normal": rec[:, 8:11], "tangent": rec[:, 12:15], "color": rec[:, 16:19],
                 "specular": rec[:, 20:23], "emission": rec[:, 24:27], "bary": rec[:, 7:12:4], "uv": rec[:, 19:24:4]}
 
+    def shadeSurface(self, hits, dirs, seeds=None, samples: int = 2):
+        """What would the renderer show for these surfaces, seen along these
+        directions (vrhip_shade_surface)?  The reference's trace with bounce
+        0's hit given by the caller and bounces 1 to 3 traced through the
+        whole scene as render() would trace it now.  hits: the (N,28) float32
+        record tensor on the renderer's GPU, contiguous, or the dict
+        traceSurface returns (its "record"); read are kind (0 a miss, 1 to 4 a
+        hit), position, normal (used as given, not normalised), tangent, color,
+        specular, emission and type.  dirs: (N,3) float32, the incoming
+        direction of each record, normalised by the library.  seeds and
+        samples as traceRadiance.  Returns an (N,4) float32 device tensor: rgb
+        the mean radiance of the paths, w 0; a record whose direction has a
+        non-finite float or zero or overflowing length, whose kind is above 4
+        or which is a hit of a type above 2 gives (0,0,0,0).
+        shadeSurface(traceSurface(o, d), d, s, k)[:, :3] is
+        traceRadiance(o, d, s, k)[:, :3] bit for bit.  ValueError for a wrong
+        device, dtype, shape or layout.  Synchronises torch's current stream
+        first; the query runs on the renderer's own stream and has finished
+        on return."""
+        import torch
+        self._need_ctx()
+        dev = self._torch_device()
+        int_types = tuple(t for t in (torch.int32, getattr(torch, "uint32", None)) if t is not None)
+        ptr = self._tensor_ptr
+        if isinstance(hits, dict):
+            hits = hits.get("record")
+        p_h = ptr("hits", hits, 28, (torch.float32,))
+        if p_h is None:
+            raise ValueError("hits and dirs are required")
+        n = int(hits.shape[0])
+        p_d = ptr("dirs", dirs, 3, (torch.float32,), n)
+        if p_d is None:
+            raise ValueError("hits and dirs are required")
+        if seeds is None:
+            seeds = torch.randint(-2**31, 2**31, (n, 2), dtype=torch.int32, device=f"cuda:{dev}")
+        p_s = ptr("seeds", seeds, 2, int_types, n)
+        out = torch.empty((n, 4), dtype=torch.float32, device=f"cuda:{dev}")
+        torch.cuda.current_stream(dev).synchronize()
+        check(self._lib.vrhip_shade_surface(self._ctx, p_h, p_d, p_s, n, int(samples),
+                                            ctypes.c_void_p(out.data_ptr())), "vrhip_shade_surface")
+        return out
+
+    def diffuseRecords(self, points, normals, color=None):
+        """The (N,28) records of a white (or `color`ed) diffuse surface at
+        these points and normals, for shadeSurface: what a lightmap texel or
+        an irradiance probe stores.  kind SURF_MESH, prim -1, type 1 (diffuse),
+        specular and emission 0, every other word 0.  points, normals: (N,3)
+        float32 torch tensors on the renderer's GPU; color: (N,3), (3,) or
+        None for (1,1,1).  The normals are normalised here, in torch: the
+        library uses a record's normal as given.  Such a record does not depend
+        on the direction passed with it; any valid one will do, for instance
+        -normals.  The result carries the reference's own weight 2 * cos on a
+        cosine-distributed sample and is not an irradiance in W/m^2 (a uniform
+        incoming radiance L gives 4/3 L).  Built in torch only."""
+        import torch
+        dev = self._torch_device()
+        ptr = self._tensor_ptr
+        if ptr("points", points, 3, (torch.float32,)) is None:
+            raise ValueError("points and normals are required")
+        n = int(points.shape[0])
+        if ptr("normals", normals, 3, (torch.float32,), n) is None:
+            raise ValueError("points and normals are required")
+        rec = torch.zeros((n, 28), dtype=torch.float32, device=f"cuda:{dev}")
+        words = rec.view(torch.int32)
+        words[:, 1] = SURF_MESH
+        words[:, 2] = -1
+        words[:, 3] = 1
+        rec[:, 4:7] = points
+        rec[:, 8:11] = normals / normals.norm(dim=1, keepdim=True)
+        if color is None:
+            rec[:, 16:19] = 1.0
+        else:
+            if not isinstance(color, torch.Tensor):
+                color = torch.tensor(color, dtype=torch.float32, device=f"cuda:{dev}")
+            if color.dtype != torch.float32 or color.device != rec.device or tuple(color.shape) not in ((3,), (n, 3)):
+                raise ValueError("color: expected (3,) or (N,3) float32 on the renderer's GPU")
+            rec[:, 16:19] = color
+        return rec
+
     def cameraRays(self):
         """The current camera's rays (vrhip_camera_rays): (origins, dirs), each
         an (H*W, 3) float32 device tensor, pixel (x, y) in row y * W + x.  The
