@@ -488,6 +488,89 @@ int vrhip_camera_rays(vrhip_ctx *ctx, float *d_origins /*float[3*W*H]*/, float *
 int vrhip_shade_surface(vrhip_ctx *ctx, const vrhip_surface_hit *d_hits /*[n], 16-byte aligned*/,
                         const float *d_dirs /*float[3n]*/, const uint32_t *d_seeds /*uint32[2n]*/,
                         uint32_t n_hits, uint32_t n_samples, float *d_radiance /*float4[n], 16-byte aligned*/);
+/* Edge-avoiding a-trous denoiser (no reference counterpart: the reference shows
+ * its accumulation unfiltered; Dammertz et al., "Edge-Avoiding A-Trous Wavelet
+ * Transform for fast Global Illumination Filtering", HPG 2010).  The step
+ * between the guides vrhip_trace_surface produces and an image: for a view at
+ * a few paths per pixel, a lightmap atlas, a probe sheet.  vrhip_denoise
+ * filters caller buffers of any grid and needs no scene and no mesh;
+ * vrhip_denoise_frame filters the context's own accumulation.
+ *   Grid: width x height cells, row-major (cell (x, y) at y * width + x).
+ *     color: float4 per cell, the mean radiance in rgb; w is carried through
+ *     untouched.  guides: one vrhip_surface_hit per cell; read are kind,
+ *     position P, normal N (used as given) and color, the albedo A.
+ *   Valid: a cell with 1 <= kind <= 4.  A miss, an invalid record and
+ *     kind > 4 make a cell invalid: it keeps its colour through every pass and
+ *     contributes to no other cell.
+ *   Arithmetic: fp32, no contraction, in exactly the order written here;
+ *     1.f / x is the IEEE quotient.  kp = 1.f / (sigma_position *
+ *     sigma_position); kc_0 = 1.f / (sigma_color * sigma_color); kc_j = kc_0 *
+ *     (float)(1u << 2j), which halves the colour sigma each pass; K = {0.375f,
+ *     0.25f, 0.0625f}, the B3 spline.
+ *   Demodulation (VRHIP_DENOISE_DEMODULATE, n_passes > 0): for a valid cell
+ *     and a channel with A.ch > 0x1p-8f, C.ch = color.ch * (1.f / A.ch) is
+ *     filtered and out.ch = C.ch * A.ch after the last pass; other channels and
+ *     other cells are filtered as given.
+ *   Pass j = 0 .. n_passes - 1, s = 1 << j, for a valid cell p = (x, y):
+ *       sum = 0 (three channels), ws = 0
+ *       for dy in -2..2 (outer), dx in -2..2 (inner):
+ *           q = (x + dx*s, y + dy*s); skipped when outside the grid or invalid
+ *                                     (no clamping, no mirroring)
+ *           h  = K[|dy|] * K[|dx|]
+ *           dn = (N_p.x*N_q.x + N_p.y*N_q.y) + N_p.z*N_q.z
+ *           wn = dn > 0 ? dn : 0   (a NaN gives 0); m times: wn = wn * wn
+ *           e  = P_q - P_p
+ *           dp = (N_p.x*e.x + N_p.y*e.y) + N_p.z*e.z
+ *           wp = 1.f / (1.f + (dp*dp) * kp)
+ *           dc = C_q - C_p
+ *           d2 = (dc.x*dc.x + dc.y*dc.y) + dc.z*dc.z
+ *           wc = 1.f / (1.f + d2 * kc_j)
+ *           w  = ((h * wn) * wp) * wc
+ *           sum.ch = sum.ch + w * C_q.ch;  ws = ws + w
+ *     with m = normal_power_log2.  When ws > 0 the new colour is C'.ch =
+ *     sum.ch * (1.f / ws), otherwise C' = C_p.  The weights are rational on
+ *     purpose: no transcendental function, so a plain C restatement
+ *     (tests/denoise_driver.c) gives the kernels' bits.  NaNs and infinities in
+ *     colours or guides propagate as this arithmetic propagates them.
+ *     n_passes = 0 copies color to out bit for bit.
+ *   Params: n_passes 0 to 8, normal_power_log2 0 to 8, flags 0 or
+ *     VRHIP_DENOISE_DEMODULATE, both sigmas finite and greater than 0.
+ *   Cost: memory-bound; per pass three float4 planes read and one written per
+ *     cell, from four float4 planes of scratch the context keeps (64 bytes a
+ *     cell, grown on demand, freed by vrhip_destroy).
+ * vrhip_denoise: device pointers on the context's device, 16-byte aligned;
+ * d_out may equal d_color.  Runs on the context stream and returns when it has
+ * finished; closes a render-service session; touches nothing resident.
+ * VRHIP_ERR_INVALID, before any device call, for a null ctx, a null array, a
+ * misaligned array, a width or height of 0 or width * height >= 2^31, null
+ * params, n_passes > 8, normal_power_log2 > 8, unknown flags, a sigma that is
+ * not finite and greater than 0, and a vrhip_create_multi context.
+ * VRHIP_ERR_NOMEM when the scratch cannot be allocated; nothing has changed.
+ * vrhip_denoise_frame: color = accum * (1.f / (float)frames) by the tonemap's
+ * own operation (rgb scaled, w as accumulated); guides = vrhip_trace_surface
+ * on vrhip_camera_rays, made in library scratch (136 more bytes a pixel; not
+ * made when n_passes = 0).  Writes d_out_f32 (float4[W*H], 16-byte aligned)
+ * and / or d_out_rgba8 (uchar4[W*H]: tone_byte(clampf(c, 0, 1)) per channel
+ * with the render's own threshold table, alpha 0xff; with n_passes = 0 the
+ * bytes of vrhip_read_rgba8); either may be NULL, not both.  The accumulation,
+ * the context's own images and the frame counter are not touched.
+ * VRHIP_ERR_INVALID, before any device call, for a null ctx, two null
+ * outputs, a misaligned output, the parameter errors above, a
+ * vrhip_create_multi context, a tiled rank (n_ranks > 1: its accumulation
+ * holds only its own tiles), 2^31 pixels or more, and when no frame has been
+ * rendered since the last clear.  VRHIP_ERR_NO_ENV in HDRI mode without an
+ * environment map, as vrhip_trace_surface.
+ * Added without an ABI version change (ABI 6 gained these symbols and changed
+ * no other). */
+enum { VRHIP_DENOISE_DEMODULATE = 1 };
+typedef struct vrhip_denoise_params {
+    uint32_t n_passes, flags, normal_power_log2;
+    float sigma_color, sigma_position;
+} vrhip_denoise_params;
+int vrhip_denoise(vrhip_ctx *ctx, const float *d_color /*float4[w*h]*/, const vrhip_surface_hit *d_guides /*[w*h]*/,
+                  uint32_t width, uint32_t height, const vrhip_denoise_params *params, float *d_out /*float4[w*h]*/);
+int vrhip_denoise_frame(vrhip_ctx *ctx, const vrhip_denoise_params *params, float *d_out_f32 /*float4[W*H] or NULL*/,
+                        uint8_t *d_out_rgba8 /*uchar4[W*H] or NULL*/);
 /* replaces vRendererCuda::loadHDR (src/vRendererCuda.cpp:320-340) +
  * cu_setHDRDim: rgba float4[w*h] (or half4 with the _half variant, the
  * Imf::Rgba layout, converted on the device). */
@@ -651,7 +734,7 @@ int vrhip_set_overlap(vrhip_ctx *ctx, int mode);
  *   vrhip_gl_present, vrhip_pack_tiles/unpack_tiles, vrhip_last_kernel_ms,
  *   vrhip_kernel_stats, vrhip_debug_counters, vrhip_set_camera, vrhip_clear,
  *   every upload (vrhip_upload_mesh_device too), vrhip_refit_mesh_device,
- *   vrhip_bvh_sah_cost, vrhip_export_mesh_flat, vrhip_trace_rays, vrhip_trace_radiance, vrhip_trace_surface, vrhip_shade_surface, vrhip_camera_rays, vrhip_set_stream, vrhip_set_tiling, vrhip_set_service
+ *   vrhip_bvh_sah_cost, vrhip_export_mesh_flat, vrhip_trace_rays, vrhip_trace_radiance, vrhip_trace_surface, vrhip_shade_surface, vrhip_camera_rays, vrhip_denoise, vrhip_denoise_frame, vrhip_set_stream, vrhip_set_tiling, vrhip_set_service
  *   (and its timing / budget hooks), vrhip_comm_init/destroy, vrhip_destroy,
  *   the counting renders, and a vrhip_render that does not fit the session.
  *   Calls that do NOT close it: the flag setters (Cornell box, example sphere,

@@ -11,6 +11,8 @@
 # With `shade`: every instantiation of the surface-record radiance kernel
 # (vr_shade*.hip) in the same table:
 #   bash scripts/kres.sh variants/<name>.log shade
+# With `denoise`: the denoiser's kernels (vr_denoise.hip):
+#   bash scripts/kres.sh variants/<name>.log denoise
 python3 - "$1" "$2" <<'PY'
 import re, sys
 recs, cur = {}, None
@@ -22,6 +24,14 @@ for line in open(sys.argv[1]):
     m = re.search(r"remark:\s+(VGPRs|VGPRs Spill|SGPRs Spill|ScratchSize \[bytes/lane\]|Occupancy \[waves/SIMD\]|LDS Size \[bytes/block\]): (\d+)", line)
     if m and cur is not None and m.group(1) not in cur:
         cur[m.group(1)] = int(m.group(2))
+if len(sys.argv) > 2 and sys.argv[2] == "denoise":
+    cols = ("VGPRs", "VGPRs Spill", "SGPRs Spill", "ScratchSize [bytes/lane]", "LDS Size [bytes/block]", "Occupancy [waves/SIMD]")
+    print(f"{'kernel':24s} {'VGPRs':>5s} {'vspill':>6s} {'sspill':>6s} {'scratch':>7s} {'LDS':>6s} {'waves':>5s}")
+    for name, r in recs.items():
+        m = re.search(r"denoise_(\w+?)_kernel", name)
+        if m:
+            print(f"{'denoise_' + m.group(1) + '_kernel':24s} " + " ".join(f"{r.get(c, 0):{w}d}" for c, w in zip(cols, (5, 6, 6, 7, 6, 5))))
+    sys.exit(0)
 QUERIES = {"radiance": ("ray_radiance_kernel", "RayRadiance"), "surface": ("ray_surface_kernel", "RaySurface"),
            "shade": ("surface_shade_kernel", "SurfaceShade")}
 if len(sys.argv) > 2 and sys.argv[2] in QUERIES:

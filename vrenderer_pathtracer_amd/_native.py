@@ -67,6 +67,8 @@ _SIGNATURES = {
     "vrhip_trace_surface": (ctypes.c_int, [_ctx, _vp, _vp, ctypes.c_uint32, _vp]),
     "vrhip_shade_surface": (ctypes.c_int, [_ctx, _vp, _vp, _vp, ctypes.c_uint32, ctypes.c_uint32, _vp]),
     "vrhip_camera_rays": (ctypes.c_int, [_ctx, _vp, _vp]),
+    "vrhip_denoise": (ctypes.c_int, [_ctx, _vp, _vp, ctypes.c_uint32, ctypes.c_uint32, _vp, _vp]),
+    "vrhip_denoise_frame": (ctypes.c_int, [_ctx, _vp, _vp, _vp]),
     "vrhip_flat_trace_rays": (ctypes.c_int, [_f, ctypes.c_size_t, _f, ctypes.c_size_t, _f, _f, _f, ctypes.c_uint32,
                                              ctypes.c_uint32, _vp]),
     "vrhip_export_mesh_flat":(ctypes.c_int, [_ctx, _f, _sz, _f, _f, _f, _f, _sz]),
@@ -130,6 +132,12 @@ _SIGNATURES = {
 }
 
 _lib = None
+
+
+class DenoiseParams(ctypes.Structure):
+    """vrhip_denoise_params."""
+    _fields_ = [("n_passes", ctypes.c_uint32), ("flags", ctypes.c_uint32), ("normal_power_log2", ctypes.c_uint32),
+                ("sigma_color", ctypes.c_float), ("sigma_position", ctypes.c_float)]
 
 
 class VRHIPError(RuntimeError):

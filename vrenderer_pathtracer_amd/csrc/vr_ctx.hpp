@@ -207,6 +207,11 @@ struct vrhip_ctx {
     hipEvent_t kev_origin = nullptr;
     std::vector<std::pair<double, double>> kev_union;
     unsigned long long* counters = nullptr;
+    // vrhip_denoise / vrhip_denoise_frame scratch, grown on demand and kept
+    // (vrhip_query.cpp): the filter's four float4 planes, and the frame call's
+    // guide records, colour plane and camera rays
+    vr4* dn_planes = nullptr; size_t dn_cells = 0;
+    uint8_t* dn_frame = nullptr; size_t dn_frame_cells = 0;
     // GL interop (colour, depth textures registered by the display host)
     hipGraphicsResource_t gl_res[2] = { nullptr, nullptr };
     // render service (vrhip_set_service): a session of launches on one

@@ -4,12 +4,15 @@
 // vr_radiance.hip), what the path tracer sees at its first hit
 // (vrhip_trace_surface, vr_surface.hip), what light leaves a surface record the
 // caller supplies (vrhip_shade_surface, vr_shade.hip), and the current camera's
-// rays to feed them (vrhip_camera_rays).  All read the scene only: the accumulation, the
-// images and the frame counter stay as they are.
+// rays to feed them (vrhip_camera_rays), and the edge-avoiding filter that turns noisy radiance and the surface
+// query's records into an image (vrhip_denoise, vrhip_denoise_frame, vr_denoise.hip).  All read the scene
+// only: the accumulation, the images and the frame counter stay as they are.
 #include <cstddef>
+#include <cmath>
 #include <cstring>
 
 #include "vr_ctx.hpp"
+#include "vr_denoise.hpp"
 #include "vr_radiance.hpp"
 #include "vr_rayquery.hpp"
 #include "vr_shade.hpp"
@@ -163,6 +166,131 @@ int vrhip_camera_rays(vrhip_ctx* c, float* d_origins, float* d_dirs)
     (void)hipGetLastError();            // the launch below reports its own error only
     const int e = vr::launch_camera_rays(p, d_origins, d_dirs, c->stream);
     if (e) return fail(VRHIP_ERR_HIP, std::string("camera rays: ") + hipGetErrorString((hipError_t)e));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return svc_verify(c);
+}
+
+// The a-trous filter (include/vrhip.h).  The checks on the parameters are
+// shared by the two calls and touch no device.
+static_assert(sizeof(vrhip_denoise_params) == 20, "five 4-byte words");
+static int denoise_params_ok(const vrhip_denoise_params* dp)
+{
+    if (!dp) return fail(VRHIP_ERR_INVALID, "null denoise params");
+    if (dp->n_passes > vr::kDenoiseMaxPasses)
+        return fail(VRHIP_ERR_INVALID, "n_passes is " + std::to_string(dp->n_passes) + " (0 to " +
+                                           std::to_string(vr::kDenoiseMaxPasses) + ")");
+    if (dp->normal_power_log2 > vr::kDenoiseMaxNormalPow)
+        return fail(VRHIP_ERR_INVALID, "normal_power_log2 is " + std::to_string(dp->normal_power_log2) + " (0 to " +
+                                           std::to_string(vr::kDenoiseMaxNormalPow) + ")");
+    if ((dp->flags & ~(uint32_t)VRHIP_DENOISE_DEMODULATE) != 0u) return fail(VRHIP_ERR_INVALID, "unknown denoise flags");
+    if (!(std::isfinite(dp->sigma_color) && dp->sigma_color > 0.f))
+        return fail(VRHIP_ERR_INVALID, "sigma_color is not finite and greater than 0");
+    if (!(std::isfinite(dp->sigma_position) && dp->sigma_position > 0.f))
+        return fail(VRHIP_ERR_INVALID, "sigma_position is not finite and greater than 0");
+    return VRHIP_OK;
+}
+
+// Grows a cached scratch buffer to `cells` cells of `bytes_per_cell`: the new
+// one is allocated before the old one goes, so a failure changes nothing.
+template <typename T>
+static int denoise_scratch(vrhip_ctx* c, T*& buf, size_t& cap, size_t cells, size_t bytes_per_cell)
+{
+    if (cap >= cells) return VRHIP_OK;
+    void* raw = nullptr;
+    if (hipMalloc(&raw, cells * bytes_per_cell) != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(VRHIP_ERR_NOMEM, "denoise scratch: " + std::to_string(cells * bytes_per_cell) + " bytes");
+    }
+    if (buf) {
+        (void)hipStreamSynchronize(c->stream);      // the last call's kernels have finished with it (the calls are synchronous)
+        (void)hipFree((void*)buf);
+    }
+    buf = (T*)raw; cap = cells;
+    return VRHIP_OK;
+}
+
+static vr::Denoise denoise_query(const vrhip_denoise_params* dp, uint32_t w, uint32_t h)
+{
+    vr::Denoise q{};
+    q.w = w; q.h = h;
+    q.n_passes = dp->n_passes; q.demodulate = (dp->flags & VRHIP_DENOISE_DEMODULATE) ? 1u : 0u;
+    q.normal_pow_log2 = dp->normal_power_log2;
+    q.sigma_color = dp->sigma_color; q.sigma_position = dp->sigma_position;
+    return q;
+}
+
+int vrhip_denoise(vrhip_ctx* c, const float* d_color, const vrhip_surface_hit* d_guides, uint32_t width, uint32_t height,
+                  const vrhip_denoise_params* dp, float* d_out)
+{
+    if (!c) return fail(VRHIP_ERR_INVALID, "null ctx");
+    if (!d_color || !d_guides || !d_out) return fail(VRHIP_ERR_INVALID, "null colour, guide or output array");
+    if (((uintptr_t)d_color & 15u) != 0u) return fail(VRHIP_ERR_INVALID, "d_color is not 16-byte aligned");
+    if (((uintptr_t)d_guides & 15u) != 0u) return fail(VRHIP_ERR_INVALID, "d_guides is not 16-byte aligned");
+    if (((uintptr_t)d_out & 15u) != 0u) return fail(VRHIP_ERR_INVALID, "d_out is not 16-byte aligned");
+    if (width == 0u || height == 0u || (uint64_t)width * height >= (1ull << 31))
+        return fail(VRHIP_ERR_INVALID, "the grid is " + std::to_string(width) + " x " + std::to_string(height) +
+                                           " (1 to 2^31 - 1 cells)");
+    int rc = denoise_params_ok(dp); if (rc) return rc;
+    if (!c->group.empty()) return refuse_multi(c, "vrhip_denoise");
+    if ((rc = set_device(c)) != VRHIP_OK) return rc;
+    if ((rc = svc_close(c)) != VRHIP_OK) return rc;
+    const size_t n = (size_t)width * height;
+    if ((rc = denoise_scratch(c, c->dn_planes, c->dn_cells, n, vr::kDenoisePlanes * sizeof(vr4))) != VRHIP_OK) return rc;
+    vr::Denoise q = denoise_query(dp, width, height);
+    q.color = (const vr4*)d_color; q.guides = (const vr::SurfaceHit*)d_guides;
+    q.planes = c->dn_planes; q.out = (vr4*)d_out;
+    (void)hipGetLastError();            // the launch below reports its own error only
+    const int e = vr::launch_denoise(q, c->stream);
+    if (e) return fail(VRHIP_ERR_HIP, std::string("denoise: ") + hipGetErrorString((hipError_t)e));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return svc_verify(c);
+}
+
+// The filter on the context's own accumulation: colour = accum * (1 / frames)
+// as the tonemap scales it, guides = the surface query on the camera's rays,
+// both made in the context's scratch.
+int vrhip_denoise_frame(vrhip_ctx* c, const vrhip_denoise_params* dp, float* d_out_f32, uint8_t* d_out_rgba8)
+{
+    if (!c) return fail(VRHIP_ERR_INVALID, "null ctx");
+    if (!d_out_f32 && !d_out_rgba8) return fail(VRHIP_ERR_INVALID, "no output array");
+    if (((uintptr_t)d_out_f32 & 15u) != 0u) return fail(VRHIP_ERR_INVALID, "d_out_f32 is not 16-byte aligned");
+    if (((uintptr_t)d_out_rgba8 & 3u) != 0u) return fail(VRHIP_ERR_INVALID, "d_out_rgba8 is not 4-byte aligned");
+    int rc = denoise_params_ok(dp); if (rc) return rc;
+    if (!c->group.empty()) return refuse_multi(c, "vrhip_denoise_frame");
+    if (c->nranks > 1u)
+        return fail(VRHIP_ERR_INVALID, "vrhip_denoise_frame: a tiled rank's accumulation holds only its own tiles");
+    if ((uint64_t)c->W * c->H >= (1ull << 31)) return fail(VRHIP_ERR_INVALID, "vrhip_denoise_frame: 2^31 pixels or more");
+    if (c->frame <= 1u) return fail(VRHIP_ERR_INVALID, "vrhip_denoise_frame: no frame rendered since the last clear");
+    if (!c->cornell && !c->hdr)
+        return fail(VRHIP_ERR_NO_ENV, "HDRI mode needs an environment map (vrhip_upload_hdr)");
+    if ((rc = set_device(c)) != VRHIP_OK) return rc;
+    if ((rc = svc_close(c)) != VRHIP_OK) return rc;
+    const size_t n = (size_t)c->W * c->H;
+    if ((rc = denoise_scratch(c, c->dn_planes, c->dn_cells, n, vr::kDenoisePlanes * sizeof(vr4))) != VRHIP_OK) return rc;
+    vr::Denoise q = denoise_query(dp, c->W, c->H);
+    q.accum = c->accum; q.coef = 1.f / (float)(c->frame - 1u);
+    q.planes = c->dn_planes; q.out = (vr4*)d_out_f32; q.out_rgba8 = (vr::u8x4*)d_out_rgba8; q.tone_t = c->tone_t;
+    (void)hipGetLastError();            // the launches below report their own errors only
+    if (dp->n_passes > 0u) {
+        // guides: 112 B a cell, then the rays, 12 + 12 B a cell
+        if ((rc = denoise_scratch(c, c->dn_frame, c->dn_frame_cells, n, sizeof(vr::SurfaceHit) + 24u)) != VRHIP_OK) return rc;
+        vr::SurfaceHit* guides = (vr::SurfaceHit*)c->dn_frame;
+        float* origins = (float*)(c->dn_frame + n * sizeof(vr::SurfaceHit));
+        float* dirs = origins + 3u * n;
+        vr::RenderParams p;
+        std::memset(&p, 0, sizeof(p));
+        camera_params(c, p);
+        int e = vr::launch_camera_rays(p, origins, dirs, c->stream);
+        if (e) return fail(VRHIP_ERR_HIP, std::string("denoise frame, camera rays: ") + hipGetErrorString((hipError_t)e));
+        std::memset(&p, 0, sizeof(p));
+        scene_params(c, p);
+        const vr::RaySurface sq{ origins, dirs, (uint32_t)n, c->mesh.a.prim_id, guides };
+        e = vr::launch_ray_surface(p, sq, mesh_stack_entries(c->mesh.a.depth), c->cu_count, c->stream);
+        if (e) return fail(VRHIP_ERR_HIP, std::string("denoise frame, guides: ") + hipGetErrorString((hipError_t)e));
+        q.guides = guides;
+    }
+    const int e = vr::launch_denoise(q, c->stream);
+    if (e) return fail(VRHIP_ERR_HIP, std::string("denoise frame: ") + hipGetErrorString((hipError_t)e));
     HIP_TRY(hipStreamSynchronize(c->stream));
     return svc_verify(c);
 }

@@ -96,6 +96,8 @@ def flat_sah_cost(flat: dict) -> float:
 RAY_MISS = 0xFFFFFFFF                    # VRHIP_RAY_MISS
 RAYS_CLOSEST, RAYS_ANY = 0, 1           # vrhip_trace_rays modes
 SURF_NONE, SURF_CORNELL, SURF_SMALL, SURF_EXAMPLE, SURF_MESH = range(5)   # vrhip_surface_hit kind (VRHIP_SURF_*)
+# VRendererHIP.denoise defaults: the minimum of the CPU sweep recorded in profiles/denoise/README.md
+DENOISE_SIGMA_COLOR, DENOISE_SIGMA_POSITION, DENOISE_NORMAL_POWER_LOG2 = 4.0, 32.0, 1
 
 
 def _unpack_hits(rec, xp):
@@ -554,6 +556,86 @@ class VRendererHIP:
         check(self._lib.vrhip_camera_rays(self._ctx, ctypes.c_void_p(o.data_ptr()), ctypes.c_void_p(d.data_ptr())),
               "vrhip_camera_rays")
         return o, d
+
+    # the defaults of denoise / denoiseFrame: chosen by the sweep in profiles/denoise/README.md
+    DENOISE_DEFAULTS = dict(passes=5, sigma_color=DENOISE_SIGMA_COLOR, sigma_position=DENOISE_SIGMA_POSITION,
+                            normal_power_log2=DENOISE_NORMAL_POWER_LOG2)
+
+    @staticmethod
+    def _denoise_params(passes, sigma_color, sigma_position, normal_power_log2, demodulate):
+        vals = (passes, normal_power_log2)
+        if any(int(v) != v or not 0 <= int(v) < 2**32 for v in vals):
+            raise ValueError("passes and normal_power_log2 are non-negative integers")
+        return _native.DenoiseParams(int(passes), 1 if demodulate else 0, int(normal_power_log2), float(sigma_color),
+                                     float(sigma_position))
+
+    def denoise(self, color, guides, passes: int = 5, sigma_color: float = DENOISE_SIGMA_COLOR,
+                sigma_position: float = DENOISE_SIGMA_POSITION, normal_power_log2: int = DENOISE_NORMAL_POWER_LOG2,
+                demodulate: bool = True, out=None):
+        """The edge-avoiding a-trous filter on the caller's own grid
+        (vrhip_denoise; the definition: include/vrhip.h): a view, a lightmap
+        atlas, a probe sheet.  color: (H,W,4) float32 torch tensor on the
+        renderer's GPU, contiguous, the mean radiance in rgb (w is carried
+        through).  guides: the (H*W,28) record tensor of traceSurface or
+        diffuseRecords, or the dict traceSurface returns; read are kind (1 to
+        4: a valid cell), position, normal and color (the albedo).  passes 0 to
+        8 at strides 1, 2, 4, ...; sigma_color and sigma_position in the units
+        of the radiance and of the positions; normal_power_log2 m: the normal
+        weight is max(N_p . N_q, 0)^(2^m); demodulate: filter colour / albedo
+        and multiply the albedo back.  The defaults are DENOISE_DEFAULTS.  Returns an
+        (H,W,4) tensor; out=color filters in place.  ValueError for a wrong
+        device, dtype, shape or layout.  Synchronises torch's current stream
+        first; the filter runs on the renderer's own stream and has finished on
+        return."""
+        import torch
+        self._need_ctx()
+        dev = self._torch_device()
+        if isinstance(guides, dict):
+            guides = guides.get("record")
+        if not isinstance(color, torch.Tensor) or color.dim() != 3 or color.shape[2] != 4:
+            raise ValueError("color: expected an (H, W, 4) torch tensor")
+        h, w = int(color.shape[0]), int(color.shape[1])
+        if h == 0 or w == 0:
+            raise ValueError("color: an empty grid")
+        p_c = self._tensor_ptr("color", color.view(h * w, 4) if color.is_contiguous() else color, 4, (torch.float32,))
+        p_g = self._tensor_ptr("guides", guides, 28, (torch.float32,), h * w)
+        if p_g is None:
+            raise ValueError("color and guides are required")
+        if out is None:
+            out = torch.empty((h, w, 4), dtype=torch.float32, device=f"cuda:{dev}")
+        elif not isinstance(out, torch.Tensor) or tuple(out.shape) != (h, w, 4):
+            raise ValueError(f"out: expected an ({h}, {w}, 4) torch tensor")
+        p_o = self._tensor_ptr("out", out.view(h * w, 4) if out.is_contiguous() else out, 4, (torch.float32,))
+        prm = self._denoise_params(passes, sigma_color, sigma_position, normal_power_log2, demodulate)
+        torch.cuda.current_stream(dev).synchronize()
+        check(self._lib.vrhip_denoise(self._ctx, p_c, p_g, w, h, ctypes.byref(prm), p_o), "vrhip_denoise")
+        return out
+
+    def denoiseFrame(self, passes: int = 5, sigma_color: float = DENOISE_SIGMA_COLOR,
+                     sigma_position: float = DENOISE_SIGMA_POSITION, normal_power_log2: int = DENOISE_NORMAL_POWER_LOG2,
+                     demodulate: bool = True, rgba8: bool = False):
+        """The rendered frames so far, filtered (vrhip_denoise_frame): colour
+        is the accumulation divided by the frame count as the tonemap divides
+        it, guides are traceSurface on cameraRays, made inside the library.
+        Parameters as denoise.  Returns the (H,W,4) float32 device tensor, and
+        with rgba8=True the pair (float image, (H,W,4) uint8 image: the
+        render's own tonemap of the filtered colour).  The accumulation, the
+        renderer's images and the frame count stay as they are.  VRHIPError
+        before the first render, on a tiled rank and on a multi-device
+        renderer."""
+        import torch
+        self._need_ctx()
+        if self._camera is not None and self._camera.is_dirty():
+            self.updateCamera()
+        dev = self._torch_device()
+        prm = self._denoise_params(passes, sigma_color, sigma_position, normal_power_log2, demodulate)
+        h, w = int(self.height), int(self.width)
+        out = torch.empty((h, w, 4), dtype=torch.float32, device=f"cuda:{dev}")
+        img = torch.empty((h, w, 4), dtype=torch.uint8, device=f"cuda:{dev}") if rgba8 else None
+        torch.cuda.current_stream(dev).synchronize()
+        check(self._lib.vrhip_denoise_frame(self._ctx, ctypes.byref(prm), ctypes.c_void_p(out.data_ptr()),
+                                            ctypes.c_void_p(img.data_ptr()) if rgba8 else None), "vrhip_denoise_frame")
+        return (out, img) if rgba8 else out
 
     def _torch_device(self) -> int:
         """The GPU index device tensors must live on (a group's first device)."""
