@@ -100,7 +100,7 @@ __device__ __forceinline__ float span_end(float a0, float a1, float b0, float b1
 
 // ---- scene constants (PathTracer.cu:107-123)
 struct Sph { float r, px, py, pz, ex, ey, ez, cr, cg, cb; int refl; };
-__device__ __forceinline__ Sph cornell_sphere(int i) {
+__host__ __device__ __forceinline__ constexpr Sph cornell_sphere(int i) {
     switch (i) {
     case 0: return { 160.f, 0.f, 160.f + 49.f, 0.f, 4.f, 3.6f, 3.2f, 0.f, 0.f, 0.f, 1 };
     case 1: return { 1e5f, 1e5f + 50.f, 0.f, 0.f, 0.075f, 0.025f, 0.025f, 0.75f, 0.25f, 0.25f, 1 };
@@ -110,7 +110,7 @@ __device__ __forceinline__ Sph cornell_sphere(int i) {
     default: return { 1e5f, 0.f, -1e5f - 50.f, 0.f, 0.f, 0.f, 0.f, 1.f, 1.f, 1.f, 1 };
     }
 }
-__device__ __forceinline__ Sph small_sphere(int i) {
+__host__ __device__ __forceinline__ constexpr Sph small_sphere(int i) {
     if (i == 0) return { 3.5f, 15.f, 0.f, 15.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0 };   // mirror
     return { 3.5f, 25.f, 0.f, 15.f, 0.f, 0.f, 0.f, 1.f, 1.f, 1.f, 1 };             // grey, Fresnel
 }
@@ -185,6 +185,76 @@ struct HitRec {
     float bu, bv;           // barycentrics for mesh hits
     float su, sv;           // example sphere texture coords (from the stale normal)
 };
+// ---- the shading pass's constants of a hit, by table (straight_shade)
+// What fill_hit and emission_of read of the sphere a Cornell-box path hit:
+// cornell_sphere(0..5) in rows 0-5, small_sphere(0..1) in rows 6-7, and in
+// row 8 what an untextured mesh hit has in the same fields (white, no
+// emission, diffuse, no specular colour; its centre is not read).  The two
+// functions stay the source of the set-up pass, where the index is a
+// compile-time constant after unrolling; the asserts below pin every entry to
+// them.  spec: the x = y = z of vHitData's specular colour.
+struct alignas(16) HitRow { float px, py, pz; int refl; float cr, cg, cb, spec; float ex, ey, ez, pad; };
+constexpr int kHitRows = 9, kMeshRow = 8;
+constexpr HitRow kHitTab[kHitRows] = {
+    { 0.f, 209.f, 0.f, 1,           0.f, 0.f, 0.f, 0.f,       4.f, 3.6f, 3.2f, 0.f },          // light
+    { 100050.f, 0.f, 0.f, 1,        0.75f, 0.25f, 0.25f, 0.f, 0.075f, 0.025f, 0.025f, 0.f },   // emitting walls
+    { -100050.f, 0.f, 0.f, 1,       0.25f, 0.75f, 0.25f, 0.f, 0.025f, 0.075f, 0.025f, 0.f },
+    { 0.f, 0.f, -100100.f, 1,       1.f, 1.f, 1.f, 0.f,       0.f, 0.f, 0.f, 0.f },
+    { 0.f, 100050.f, 0.f, 1,        1.f, 1.f, 1.f, 0.f,       0.f, 0.f, 0.f, 0.f },
+    { 0.f, -100050.f, 0.f, 1,       1.f, 1.f, 1.f, 0.f,       0.f, 0.f, 0.f, 0.f },
+    { 15.f, 0.f, 15.f, 0,           0.f, 0.f, 0.f, 1.f,       0.f, 0.f, 0.f, 0.f },            // mirror
+    { 25.f, 0.f, 15.f, 1,           1.f, 1.f, 1.f, 1.f,       0.f, 0.f, 0.f, 0.f },            // grey, Fresnel
+    { 0.f, 0.f, 0.f, 1,             1.f, 1.f, 1.f, 0.f,       0.f, 0.f, 0.f, 0.f },            // mesh
+};
+constexpr bool hit_row_is(const HitRow& t, const Sph& s, float spec) {
+    return t.px == s.px && t.py == s.py && t.pz == s.pz && t.refl == s.refl && t.cr == s.cr && t.cg == s.cg &&
+           t.cb == s.cb && t.spec == spec && t.ex == s.ex && t.ey == s.ey && t.ez == s.ez && t.pad == 0.f;
+}
+static_assert(hit_row_is(kHitTab[0], cornell_sphere(0), 0.f) && hit_row_is(kHitTab[1], cornell_sphere(1), 0.f) &&
+              hit_row_is(kHitTab[2], cornell_sphere(2), 0.f) && hit_row_is(kHitTab[3], cornell_sphere(3), 0.f) &&
+              hit_row_is(kHitTab[4], cornell_sphere(4), 0.f) && hit_row_is(kHitTab[5], cornell_sphere(5), 0.f),
+              "kHitTab rows 0-5 are cornell_sphere(0..5), specular colour 0");
+static_assert(hit_row_is(kHitTab[6], small_sphere(0), 1.f) && hit_row_is(kHitTab[7], small_sphere(1), 1.f),
+              "kHitTab rows 6-7 are small_sphere(0..1), specular colour 1");
+static_assert(hit_row_is(kHitTab[kMeshRow], Sph{ 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 1.f, 1.f, 1.f, 1 }, 0.f),
+              "kHitTab row 8 is an untextured mesh hit (fill_hit)");
+static_assert(sizeof(HitRow) == 48, "three 16-byte reads per row");
+__device__ __forceinline__ int hit_row(const HitRec& hr) {
+    return hr.kind == HK_CORNELL ? hr.idx : hr.kind == HK_SMALL ? 6 + hr.idx : kMeshRow;
+}
+// The gate: VR_STRAIGHT_SHADE in the kernels whose bounce step is SHADE_ONLY,
+// i.e. the retire_first kernels -- C2's service, whole-frame and shard kernels
+// and the Cornell mesh class.  Off in every other kernel: the one-frame and
+// small-launch kernels, the HDRI kernels, the generic kernel (F_STRICT, the
+// example sphere), the reference-algorithm counting variant and the radiance /
+// surface / shade query units, which all keep the switch and the per-kind
+// arms.  Measured (C2, 16-frame steps, three alternations, same hash,
+// profiles/straight_shade/): the table in LDS with one normalisation +3.1 %,
+// with a normalisation per arm +2.0 %; the rows from one compare each and a
+// v_cndmask chain per field +1.5 % and +0.1 %; one normalisation on the
+// switch +1.7 %.  VR_STRAIGHT_SHADE 0: off.
+#ifndef VR_STRAIGHT_SHADE
+#define VR_STRAIGHT_SHADE 1
+#endif
+constexpr bool straight_shade() { return VR_STRAIGHT_SHADE != 0; }
+// The block's copy of kHitTab (lds_setup): a static LDS array of the kernels
+// that name it, 432 B, which their node cache gives up (hit_tab_bytes).
+__device__ __forceinline__ vr4* hit_tab_lds() {
+    __shared__ vr4 tab[3 * kHitRows];
+    return tab;
+}
+// The row of a hit, read per lane with no control flow (a mesh lane's row is
+// row 8); the emission alone for the retirement.
+__device__ __forceinline__ HitRow hit_row_get(const HitRec& hr) {
+    const vr4* t = hit_tab_lds() + 3 * hit_row(hr);
+    const vr4 a = t[0], b = t[1], c = t[2];
+    return { a.x, a.y, a.z, __float_as_int(a.w), b.x, b.y, b.z, b.w, c.x, c.y, c.z, c.w };
+}
+__device__ __forceinline__ vr4 hit_row_emission(const HitRec& hr) {
+    const vr4 c = hit_tab_lds()[3 * hit_row(hr) + 2];
+    return mk4(c.x, c.y, c.z, 0.f);
+}
+
 // Per-lane event counts for the counting variant (algorithmic bytes).
 struct Cnt {
     uint32_t rays = 0, nodes = 0, slots = 0, tris = 0, attr = 0, tex = 0, hdr = 0, brdf = 0;
@@ -768,11 +838,75 @@ __device__ __forceinline__ bool intersect_scene(const RenderParams& p, const Ray
 // (C2 16-frame steps +0.7 %, C5 one frame per call -1 %, r05s)
 template <uint32_t FEAT>
 constexpr bool face_from_edges() { return !((FEAT & F_INLINE_PRIM) != 0u && (FEAT & F_CORNELL) != 0u); }
-template <uint32_t FEAT>
+// STRAIGHT (straight_shade: the kernels whose shading pass holds only hits
+// of the Cornell box's spheres and the mesh): the constants of the hit from
+// its row of kHitTab instead of a switch on the sphere's index, one hit point,
+// and one normalize4 of the normal selected per lane -- hp - centre for a
+// sphere, cross4(e1, e2) or the mapped normal for the mesh.  A pass of a
+// retire_first kernel holds hits on several walls, the light and the mesh, so
+// it walked every arm of the switch and every arm's normalisation one after
+// another.  The operations on a lane and their order are the other form's
+// (inv_sqrt_exact's vote picks between two sequences of the same result), so
+// is every bit of h.
+template <uint32_t FEAT, bool STRAIGHT = false>
 __device__ __forceinline__ void fill_hit(const RenderParams& p, const Ray& r, const HitRec& hr, Hit& h)
 {
     h.tan = mk4(0.f, 0.f, 0.f, 0.f);
     const bool view_brdf = HAS(F_VIEW_BRDF);
+    if constexpr (STRAIGHT) {
+        static_assert((FEAT & F_EXAMPLE) == 0u && (FEAT & F_CORNELL) != 0u && face_from_edges<FEAT>(), "Cornell mesh path pool");
+        const HitRow s = hit_row_get(hr);
+        h.hp = add4(r.o, mul4s(r.d, hr.t));
+        vr4 nraw = sub4(h.hp, mk4(s.px, s.py, s.pz, 0.f));
+        h.col = mk4(s.cr, s.cg, s.cb, 0.f);
+        h.em = mk4(s.ex, s.ey, s.ez, 0.f);
+        h.type = (unsigned)s.refl;
+        h.spec = mk4(s.spec, s.spec, s.spec, 0.f);
+        if (hr.kind == HK_MESH) {
+            // the attribute loads stay with the mesh lanes (the texture path
+            // charges per active lane)
+            const int a = hr.idx;
+            constexpr bool MAPS = (FEAT & (F_TEX_DIFF | F_TEX_NORM | F_TEX_SPEC | F_VIEW_BRDF | F_BRDF)) != 0u;
+            bool mapped = false;
+            if constexpr (MAPS) {
+                const float b0 = 1.f - hr.bu - hr.bv;
+                const vr2 uv0 = p.uvs[a], uv1 = p.uvs[a + 1], uv2 = p.uvs[a + 2];
+                const float uvx = (b0 * uv0.x + hr.bu * uv1.x) + hr.bv * uv2.x;
+                const float uvy = (b0 * uv0.y + hr.bu * uv1.y) + hr.bv * uv2.y;
+                vr4 tangent = normalize4(add4(add4(muls4(b0, p.tangents[a]), muls4(hr.bu, p.tangents[a + 1])),
+                                              muls4(hr.bv, p.tangents[a + 2])));
+                tangent.w = 0.f;
+                if (HAS(F_TEX_DIFF) && !view_brdf)
+                    h.col = p.tex[0][tex_addr(p.tex_w[0], p.tex_h[0], uvx, uvy)];
+                if (HAS(F_TEX_NORM) && dot4(tangent, tangent) > VR_EPS) {
+                    const int ta = tex_addr(p.tex_w[1], p.tex_h[1], uvx, uvy);
+                    vr4 normal = normalize4(add4(add4(muls4(b0, p.normals[a]), muls4(hr.bu, p.normals[a + 1])),
+                                                 muls4(hr.bv, p.normals[a + 2])));
+                    normal.w = 0.f;
+                    const vr4 bitangent = cross4(normal, tangent);
+                    const vr4 nm = normalize4(sub4(muls4(2.f, p.tex[1][ta]), mk4(1.f, 1.f, 1.f, 0.f)));
+                    nraw = tbn_mul(tangent, bitangent, normal, nm);
+                    mapped = true;
+                }
+                if (HAS(F_TEX_SPEC) && !view_brdf)
+                    h.spec = p.tex[2][tex_addr(p.tex_w[2], p.tex_h[2], uvx, uvy)];
+                h.tan = tangent;
+                h.type = view_brdf ? 2u : 1u;
+            }
+            if (!mapped) {
+                // (the face normal from the traversal's copy of the triangle: below)
+                const __amdgpu_buffer_rsrc_t tbuf = buf_rsrc(p.tri_e, p.n_tris * 36u);
+                const int o = (a / 3) * 36;
+                const vr_u32x3 q1 = __builtin_amdgcn_raw_buffer_load_b96(tbuf, o + 12, 0, 0);
+                const vr_u32x3 q2 = __builtin_amdgcn_raw_buffer_load_b96(tbuf, o + 24, 0, 0);
+                const vr4 e1 = mk4(__uint_as_float(q1.x), __uint_as_float(q1.y), __uint_as_float(q1.z), 0.f);
+                const vr4 e2 = mk4(__uint_as_float(q2.x), __uint_as_float(q2.y), __uint_as_float(q2.z), 0.f);
+                nraw = cross4(e1, e2);
+            }
+        }
+        h.n = normalize4(nraw);
+        return;
+    }
     if (hr.kind == HK_CORNELL || hr.kind == HK_SMALL) {
         const Sph s = hr.kind == HK_CORNELL ? cornell_sphere(hr.idx) : small_sphere(hr.idx);
         h.hp = add4(r.o, mul4s(r.d, hr.t));
@@ -863,7 +997,10 @@ __device__ __forceinline__ void fill_hit(const RenderParams& p, const Ray& r, co
 }
 
 // Emission of a hit (the only vHitData field the last bounce observes).
+// (STRAIGHT: from the hit's row of kHitTab, as fill_hit)
+template <bool STRAIGHT = false>
 __device__ __forceinline__ vr4 emission_of(const HitRec& hr) {
+    if constexpr (STRAIGHT) return hit_row_emission(hr);
     if (hr.kind == HK_CORNELL || hr.kind == HK_SMALL) {
         const Sph s = hr.kind == HK_CORNELL ? cornell_sphere(hr.idx) : small_sphere(hr.idx);
         return mk4(s.ex, s.ey, s.ez, 0.f);
@@ -1052,7 +1189,7 @@ __device__ __forceinline__ bool path_ends_short(const HitRec& hr, const PathStat
 {
     return !(hr.t < 1e20f) || ps.bounce == 3;
 }
-template <typename Sink>
+template <bool STRAIGHT = false, typename Sink>
 __device__ __forceinline__ void end_short(const HitRec& hr, PathState& ps, vr4& out, const Sink& sink)
 {
     if (!(hr.t < 1e20f)) {
@@ -1067,7 +1204,7 @@ __device__ __forceinline__ void end_short(const HitRec& hr, PathState& ps, vr4& 
     }
     // last bounce: only the emission term is observable; the material
     // branch would only prepare a ray that is never traced
-    ps.accum = add4(ps.accum, mul4(ps.mask, emission_of(hr)));
+    ps.accum = add4(ps.accum, mul4(ps.mask, emission_of<STRAIGHT>(hr)));
     ps.accum.w = ps.depth;
     out = ps.accum;
     sink(out);
@@ -1147,7 +1284,7 @@ __device__ __forceinline__ bool bounce_step(const RenderParams& p, Ray& ray, con
     // whose camera ray leaves the box)
     if constexpr (SHADE_ONLY) { if (!hit) return true; }
     Hit h;
-    fill_hit<FEAT>(p, ray, hr, h);
+    fill_hit<FEAT, SHADE_ONLY && straight_shade()>(p, ray, hr, h);
     if constexpr (SPEC && VR_SPEC_SAMPLE == 1) spec_sample();
     if (COUNT) {
         if (hr.kind == HK_MESH) {
@@ -1365,7 +1502,9 @@ __device__ __forceinline__ void store_path_rgb(const RenderParams& p, uint32_t q
 
 // Binds this thread's stack column and fills the block's node cache with
 // the first nodes of the area-ordered node array.
-template <uint32_t FEAT, int BT = kBlockThreads>
+// HIT_TAB: also the block's copy of kHitTab (straight_shade), which the
+// barrier below publishes.
+template <uint32_t FEAT, int BT = kBlockThreads, bool HIT_TAB = false>
 __device__ __forceinline__ Lds lds_setup(const RenderParams& p, int* lds_stack, vr4* lds_nodes, int2* lds_idx,
                                          int cn, int tid)
 {
@@ -1375,6 +1514,16 @@ __device__ __forceinline__ Lds lds_setup(const RenderParams& p, int* lds_stack, 
     L.nodes = lds_nodes;
     L.idx = lds_idx;
     L.n_cached = 0;
+    if constexpr (HIT_TAB && straight_shade()) {
+        static_assert((FEAT & F_MESH) != 0u, "published by the node cache's barrier");
+        if (tid < kHitRows) {
+            const HitRow s = kHitTab[tid];
+            vr4* t = hit_tab_lds() + 3 * tid;
+            t[0] = mk4(s.px, s.py, s.pz, __int_as_float(s.refl));
+            t[1] = mk4(s.cr, s.cg, s.cb, s.spec);
+            t[2] = mk4(s.ex, s.ey, s.ez, s.pad);
+        }
+    }
     if (HAS(F_MESH)) {
         if (!HAS(F_STRICT)) {            // fp16 nodes, 32 B: 1.5x as many fit
             const uint32_t cap = (uint32_t)(3 * cn / 2);
@@ -1876,9 +2025,34 @@ constexpr int path_waves(int stack, bool c) {
 constexpr int path_blocks_per_cu(int stack, int bt, bool c) { return 4 * path_waves(stack, c) * 64 / bt; }
 // LDS per block: an equal share of the CU's 160 KB less 256 B per 256 threads;
 // the node cache takes what the stacks leave (56 B per node)
-constexpr int path_cache_nodes(int stack, int bt, bool c) {
-    return (163840 / path_blocks_per_cu(stack, bt, c) - bt - stack * bt * 4) / 56 > 0
-               ? (163840 / path_blocks_per_cu(stack, bt, c) - bt - stack * bt * 4) / 56 : 1;
+// (extra: bytes of other static LDS taken out of the cache's share)
+constexpr int path_cache_nodes(int stack, int bt, bool c, int extra = 0) {
+    return (163840 / path_blocks_per_cu(stack, bt, c) - bt - stack * bt * 4 - extra) / 56 > 0
+               ? (163840 / path_blocks_per_cu(stack, bt, c) - bt - stack * bt * 4 - extra) / 56 : 1;
+}
+// The retire_first kernels' copy of kHitTab (hit_tab_lds) comes out of the
+// node cache (profiles/r06g measured the cache as neutral in these kernels),
+// so that it never costs a block per CU: with the table on top, the 24-entry
+// kernels in 256-thread blocks went from 21 to 22 allocation granules of
+// 1,280 B, and six blocks of 22 do not fit the CU's 128.  path_lds_fits: the
+// blocks of one CU at their allocated size -- the stacks, 48 B per cached node
+// (no retire_first kernel has F_STRICT, and without it lds_idx is never read
+// and takes no LDS), the table and kPathLdsOther for the bodies' own words
+// (the service body's ring state is the largest, 144 B) -- fit in 160 KB.
+template <uint32_t FEAT>
+constexpr int hit_tab_bytes() { return retire_first<FEAT>() && straight_shade() ? 3 * kHitRows * 16 : 0; }
+constexpr int kLdsGranule = 1280, kPathLdsOther = 160;
+constexpr bool path_lds_fits(int stack, int bt, bool c, int cn, int tab) {
+    return path_blocks_per_cu(stack, bt, c) *
+           ((stack * bt * 4 + 48 * cn + tab + kPathLdsOther + kLdsGranule - 1) / kLdsGranule) * kLdsGranule <= 163840;
+}
+// The node cache of a kernel that holds the table: the share less the table,
+// and less whole nodes until the blocks fit (the share itself is not a
+// multiple of the granule).
+constexpr int path_cache_nodes_tab(int stack, int bt, bool c, int tab) {
+    int cn = path_cache_nodes(stack, bt, c, tab);
+    while (tab != 0 && cn > 1 && !path_lds_fits(stack, bt, c, cn, tab)) --cn;
+    return cn;
 }
 // The Cornell-box render-service kernels take the 7-wave residency of the
 // Cornell path kernels (r05: with the single refill site and the polynomial
@@ -1948,11 +2122,13 @@ constexpr bool lds_q() {
 template <int STACK, uint32_t FEAT, int BT>
 __global__ void __launch_bounds__(BT, path_waves(STACK, cornell_kernel<FEAT>())) render_wave_kernel(const RenderParams p)
 {
-    constexpr int CN = path_cache_nodes(STACK, BT, cornell_kernel<FEAT>()) - (lds_q<FEAT>() ? (4 * BT + 55) / 56 : 0);
+    constexpr int CN = path_cache_nodes_tab(STACK, BT, cornell_kernel<FEAT>(), hit_tab_bytes<FEAT>()) - (lds_q<FEAT>() ? (4 * BT + 55) / 56 : 0);
+    static_assert(hit_tab_bytes<FEAT>() == 0 || path_lds_fits(STACK, BT, cornell_kernel<FEAT>(), CN, hit_tab_bytes<FEAT>()),
+                  "the hit table must not cost a block per CU");
     __shared__ int lds_stack[STACK * BT];
     __shared__ vr4 lds_nodes[3 * CN];
     __shared__ int2 lds_idx[CN];
-    const Lds L = lds_setup<FEAT, BT>(p, lds_stack, lds_nodes, lds_idx, CN, (int)threadIdx.x);
+    const Lds L = lds_setup<FEAT, BT, retire_first<FEAT>()>(p, lds_stack, lds_nodes, lds_idx, CN, (int)threadIdx.x);
     wave_body<STACK, FEAT, BT>(p, L);
 }
 
@@ -2174,7 +2350,7 @@ __device__ __forceinline__ void wave_body(const RenderParams& p, const Lds& L)
                         const bool rt = state == LS_SHADE && path_ends_short(hr, ps);
                         if (rt) {
                             vr4 out;
-                            end_short(hr, ps, out, [&](const vr4& o) { store_path_rgb(p, lane_q(), lane_slot(), o); });
+                            end_short<straight_shade()>(hr, ps, out, [&](const vr4& o) { store_path_rgb(p, lane_q(), lane_slot(), o); });
                         }
                         refill(rt);
                         break;
@@ -2589,7 +2765,7 @@ __device__ __forceinline__ void service_body(const RenderParams& p, const Lds& L
                         const bool rt = state == LS_SHADE && path_ends_short(hr, ps);
                         if (rt) {
                             vr4 out;
-                            end_short(hr, ps, out, [&](const vr4& o) { svc_store_path(p, q >> 8, q & 0xffu, slot, o); });
+                            end_short<straight_shade()>(hr, ps, out, [&](const vr4& o) { svc_store_path(p, q >> 8, q & 0xffu, slot, o); });
                         }
                         over = !refill(rt);
                         break;
@@ -2648,11 +2824,13 @@ __device__ __forceinline__ void service_body(const RenderParams& p, const Lds& L
 template <int STACK, uint32_t FEAT, int BT>
 __global__ void __launch_bounds__(BT, path_waves(STACK, cornell_kernel<FEAT>())) render_service_kernel(const RenderParams p)
 {
-    constexpr int CN = path_cache_nodes(STACK, BT, cornell_kernel<FEAT>());
+    constexpr int CN = path_cache_nodes_tab(STACK, BT, cornell_kernel<FEAT>(), hit_tab_bytes<FEAT>());
+    static_assert(hit_tab_bytes<FEAT>() == 0 || path_lds_fits(STACK, BT, cornell_kernel<FEAT>(), CN, hit_tab_bytes<FEAT>()),
+                  "the hit table must not cost a block per CU");
     __shared__ int lds_stack[STACK * BT];
     __shared__ vr4 lds_nodes[3 * CN];
     __shared__ int2 lds_idx[CN];
-    const Lds L = lds_setup<FEAT, BT>(p, lds_stack, lds_nodes, lds_idx, CN, (int)threadIdx.x);
+    const Lds L = lds_setup<FEAT, BT, retire_first<FEAT>()>(p, lds_stack, lds_nodes, lds_idx, CN, (int)threadIdx.x);
     service_body<STACK, FEAT, BT>(p, L);
 }
 
