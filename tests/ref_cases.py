@@ -27,6 +27,12 @@ FEATURE_CLASSES = ["C2D", "C3D", "C2N", "C3B", "C1T", "C4D", "CB", "C3X"]     # 
 SHADING_CASES = ("S_odd_C3", "S_tall_C3B", "S_tall_C2N", "S_dot_C1T", "S_odd_C4D", "U_C3", "U_C2N", "D_tan0_C3B",
                  "D_nrm0_third_C3", "V_texels01_C3", "V_hdr_inf_C3", "S_tall_C3", "S_dot_C3X", "D_tan0_third_C2N")
 
+# the launch scalars of tests/launch_scalar_cases.py on which the oracle's restatement (the uint32 wrap of the pixel
+# seeds, the camera's operation order, pow at its edges) is checked against the reference itself: two times of 2^24
+# and more on C2, three cameras and two Fresnel pairs on C3, and a single column of tiles
+SCALAR_CASES = ("T_2p24p1_C2", "T_2p32m1_C2", "K_skewed_C3", "K_fov_10_C3", "K_up_C3", "F_0_0.5_C3", "F_1_64_C3",
+                "I_16x64_C2")
+
 # name -> (family file, recipe, parameters)
 CASES = {
     "C1": ("configs", "config", dict(cfg="C1", frames=3)),
@@ -51,6 +57,8 @@ CASES = {
     "C3_sbvh": ("sbvh", "sbvh", dict(cfg="C3")),
     # odd map shapes, wild uvs, zero attributes, extreme texels: recipes in tests/shading_cases.py
     **{n: ("shading", "shading", dict(case=n)) for n in SHADING_CASES},
+    # time seeds, cameras, Fresnel pairs and an image shape: recipes in tests/launch_scalar_cases.py
+    **{n: ("scalars", "scalars", dict(case=n)) for n in SCALAR_CASES},
 }
 # cases in which no primary hit lies farther than the depth byte's range
 # (150 units), so the depth image compares on every pixel
@@ -61,6 +69,9 @@ FAMILIES = sorted({v[0] for v in CASES.values()})
 
 
 def times_of(name):
+    if CASES[name][1] == "scalars":
+        import launch_scalar_cases
+        return launch_scalar_cases.ref_times(CASES[name][2]["case"])
     frames = CASES[name][2].get("frames", 2)
     return [12345 + 1009 * i for i in range(frames)]
 
@@ -138,6 +149,9 @@ def make_case(name, stored=None):
     elif recipe == "shading":
         import shading_cases
         sc = shading_cases.make_case(p["case"])
+    elif recipe == "scalars":
+        import launch_scalar_cases
+        sc = launch_scalar_cases.ref_scene(p["case"])
     else:
         raise ValueError(recipe)
     sc["name"] = name

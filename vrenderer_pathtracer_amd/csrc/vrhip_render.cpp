@@ -412,8 +412,9 @@ static LaunchPlan launch_decisions(const vrhip_ctx* c, const RenderCall& q, vr::
     // on (vrhip_set_kernel_timing): recorded on the stream around the
     // render kernels they cost ≈ 8 µs per synchronous one-frame call
     d.timed = q.n_tiles && c->kernel_timing;
+    // (a rank without a tile launches nothing: there is no kernel node to capture)
     d.graph = c->use_graph && count == 0 && q.wave_kernel && k == 1u && !d.on_lane && !d.timed && p.inline_prim &&
-              p.use_scratch;
+              p.use_scratch && q.n_tiles > 0;
     d.arm = c->sync_flag_mode && count == 0 && k == q.n_frames && done == 0 && !d.on_lane && p.use_scratch &&
             q.n_tiles > 0 && q.n_tiles <= VR_SYNC_FLAG_MAX_TILES && !c->comm && c->group.empty() && !c->stream_shared;
     return d;
