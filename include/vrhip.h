@@ -424,6 +424,98 @@ int vrhip_trace_surface(vrhip_ctx *ctx, const float *d_origins /*float[3n]*/, co
  * before any device call, for a null ctx, a null array, and a
  * vrhip_create_multi context. */
 int vrhip_camera_rays(vrhip_ctx *ctx, float *d_origins /*float[3*W*H]*/, float *d_dirs /*float[3*W*H]*/);
+/* The surface record at a point of the resident mesh, with no ray (no
+ * reference counterpart): the record vrhip_trace_surface would write for a hit
+ * of triangle prims[i] at barycentrics (u, v) = d_bary[2i], d_bary[2i + 1].
+ *   prim: the triangle exactly as vrhip_trace_rays names it: after
+ *     vrhip_upload_mesh_device[_ex] (also after a refit) the row of tris, after
+ *     vrhip_upload_mesh_flat / _indexed the flat slot of its first vertex.
+ *   u, v are used as given, not clamped: extrapolation is the caller's business.
+ *   Record: kind = VRHIP_SURF_MESH, prim, bary_u = u, bary_v = v, t = 0.
+ *     position has no hit-point form without a ray: per component it is
+ *     (b0 * v0 + u * v1) + v * v2 in fp32 with b0 = 1.f - u - v evaluated left
+ *     to right, the shape of tex_u and tex_v.  Every other word is what the
+ *     mesh hit of vrhip_trace_surface holds, computed by the same device code on
+ *     the same operands in the same order: the mapped normal where a normal map
+ *     is loaded and the tangent is usable and the face normal otherwise, the
+ *     tangent, color after the diffuse map, specular, emission 0, type 2 under
+ *     the BRDF view and 1 otherwise, tex_u, tex_v; the pads are 0.
+ *   Scene: the maps and the BRDF-view flag apply as vrhip_render would apply
+ *     them now; the Cornell-box and example-sphere flags have no effect, as in
+ *     vrhip_trace_rays; no environment map is needed.
+ *   Invalid: an entry whose prim names no resident triangle (out of range, a
+ *     flat slot that is no triangle's first vertex, VRHIP_RAY_MISS) or whose u
+ *     or v is not finite gives 28 zero words; it is classified before any
+ *     attribute load.
+ * The prim -> triangle lookup is the inverse of what vrhip_trace_rays reports;
+ * it is built on the device at the first call after an upload (where a caller
+ * triangle is stored more than once, the first stored copy is taken) and kept
+ * until the next upload; a refit keeps it.  Nothing else resident is touched.
+ * Runs on the context stream and returns when it has finished; closes a
+ * render-service session.  VRHIP_ERR_INVALID, before any device call, for a
+ * null ctx, a null array with n > 0, a misaligned d_hits, a
+ * vrhip_create_multi context, and no mesh loaded, checked in that order and
+ * whatever n is: as in vrhip_trace_rays the mesh comes before "nothing to do".
+ * Then n == 0: VRHIP_OK, nothing written, no device call.
+ * Added without an ABI version change. */
+int vrhip_surface_at(vrhip_ctx *ctx, const uint32_t *d_prims /*[n]*/, const float *d_bary /*float[2n]: u, v*/,
+                     uint32_t n, vrhip_surface_hit *d_hits /*[n], 16-byte aligned*/);
+/* The surface records of a width x height lightmap atlas of the resident
+ * mesh's uvs (no reference counterpart): the first stage of a bake,
+ *   vrhip_atlas_surface -> vrhip_shade_surface -> vrhip_denoise ->
+ *   vrhip_upload_texture(diffuse) -> vrhip_render.
+ * Texel (x, y) is record y * width + x; its centre is
+ *   cx = ((double)x + 0.5) / (double)width, cy = ((double)y + 0.5) / (double)height,
+ * so the texel the renderer's map fetch addresses for (u, v) -- x = (int)(width
+ * * u), y = (int)(height * v) -- is the texel that contains (u, v).
+ * THE DEFINITION.  Everything is fp64 + - * / without contraction, correctly
+ * rounded; no sqrt, no libm.
+ *   Triangle: the uvs a, b, c of its three vertex slots widened to double.  A
+ *     triangle with a non-finite uv covers nothing.
+ *   Edge function, canonical per edge: order the endpoints of edge (p, q) as
+ *     p' < q' by (x, then y);
+ *       E = (q'x - p'x) * (cy - p'y) - (q'y - p'y) * (cx - p'x),
+ *     negated if the endpoints were swapped.  Two triangles that share an edge
+ *     compute the same magnitude with opposite signs, so a texel centre on a
+ *     shared edge is never lost between them.
+ *   Coverage: A2 is the edge function of (a, b) evaluated at c.  A2 == 0 or
+ *     not finite: the triangle covers nothing.  A2 > 0: the centre is covered
+ *     iff the edge values of (a, b), (b, c), (c, a) are all >= 0; A2 < 0: iff
+ *     all three are <= 0.  Both windings count (mirrored charts are legal).
+ *   Winner: among the triangles that cover a centre the smallest prim (in the
+ *     caller's terms, as vrhip_surface_at) wins, whatever the builder, the tree
+ *     and the order the triangles are stored in.
+ *   Barycentrics of the winner, plain (not canonical) forms, c.x, c.y vertex c:
+ *       eu = (cx - a.x) * (c.y - a.y) - (cy - a.y) * (c.x - a.x),
+ *       ev = (b.x - a.x) * (cy - a.y) - (b.y - a.y) * (cx - a.x),
+ *       ud = eu / A2, vd = ev / A2,
+ *       u = (float)clamp(ud, 0, 1), v = (float)clamp(vd, 0, 1)
+ *     (clamp(x, 0, 1) = x < 0 ? 0 : x > 1 ? 1 : x), and if the fp32 sum
+ *     u + v > 1.f then v = 1.f - u.
+ *   Record: a covered texel gets vrhip_surface_at(prim, u, v)'s record, t = 0;
+ *     an uncovered one the miss record of vrhip_trace_surface (t = 1e20, kind
+ *     0, prim VRHIP_RAY_MISS, every other word 0).
+ *   Gutter: `gutter` dilation passes, 0 to 64.  In pass k = 1 .. gutter a texel
+ *     still uncovered after pass k - 1 looks at its eight neighbours in the
+ *     order (x-1,y) (x+1,y) (x,y-1) (x,y+1) (x-1,y-1) (x+1,y-1) (x-1,y+1)
+ *     (x+1,y+1), those inside the atlas only (no wrap), and takes the (prim, u,
+ *     v) of the first that was covered after pass k - 1; its record is that
+ *     neighbour's with t = (float)k.  vrhip_shade_surface and vrhip_denoise do
+ *     not read t; here it is the texel's distance from coverage.  The gutter
+ *     exists because the renderer fetches maps by truncation: a hit near a
+ *     chart's border can land in a texel whose centre the chart does not
+ *     cover, and without a gutter that texel of the baked map is black.
+ *   Limits: 1 <= width, height <= 16384, width * height <= 2^26.
+ * Scene dependence as vrhip_surface_at.  Runs on the context stream and
+ * returns when it has finished; closes a render-service session; touches
+ * nothing resident.  VRHIP_ERR_INVALID, before any device call, for a null
+ * ctx, a null or misaligned d_hits, a size or gutter out of range, a
+ * vrhip_create_multi context, and no mesh loaded.
+ * Cost: scratch of 32 bytes per texel kept with the context; one 64-bit integer
+ * atomic minimum per (covering triangle, texel), seven 16-byte stores per
+ * texel (profiles/atlas).  Added without an ABI version change. */
+int vrhip_atlas_surface(vrhip_ctx *ctx, uint32_t width, uint32_t height, uint32_t gutter,
+                        vrhip_surface_hit *d_hits /*[width*height], 16-byte aligned*/);
 /* Radiance from the caller's surface records (no reference counterpart as a
  * call): what would the renderer show for this surface, seen from this
  * direction?  For lightmap texels and irradiance probes, whose points and
@@ -734,7 +826,7 @@ int vrhip_set_overlap(vrhip_ctx *ctx, int mode);
  *   vrhip_gl_present, vrhip_pack_tiles/unpack_tiles, vrhip_last_kernel_ms,
  *   vrhip_kernel_stats, vrhip_debug_counters, vrhip_set_camera, vrhip_clear,
  *   every upload (vrhip_upload_mesh_device too), vrhip_refit_mesh_device,
- *   vrhip_bvh_sah_cost, vrhip_export_mesh_flat, vrhip_trace_rays, vrhip_trace_radiance, vrhip_trace_surface, vrhip_shade_surface, vrhip_camera_rays, vrhip_denoise, vrhip_denoise_frame, vrhip_set_stream, vrhip_set_tiling, vrhip_set_service
+ *   vrhip_bvh_sah_cost, vrhip_export_mesh_flat, vrhip_trace_rays, vrhip_trace_radiance, vrhip_trace_surface, vrhip_shade_surface, vrhip_camera_rays, vrhip_surface_at, vrhip_atlas_surface, vrhip_denoise, vrhip_denoise_frame, vrhip_set_stream, vrhip_set_tiling, vrhip_set_service
  *   (and its timing / budget hooks), vrhip_comm_init/destroy, vrhip_destroy,
  *   the counting renders, and a vrhip_render that does not fit the session.
  *   Calls that do NOT close it: the flag setters (Cornell box, example sphere,

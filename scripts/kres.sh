@@ -13,6 +13,8 @@
 #   bash scripts/kres.sh variants/<name>.log shade
 # With `denoise`: the denoiser's kernels (vr_denoise.hip):
 #   bash scripts/kres.sh variants/<name>.log denoise
+# With `atlas`: the atlas and surface-at kernels (vr_atlas.hip):
+#   bash scripts/kres.sh variants/<name>.log atlas
 python3 - "$1" "$2" <<'PY'
 import re, sys
 recs, cur = {}, None
@@ -31,6 +33,15 @@ if len(sys.argv) > 2 and sys.argv[2] == "denoise":
         m = re.search(r"denoise_(\w+?)_kernel", name)
         if m:
             print(f"{'denoise_' + m.group(1) + '_kernel':24s} " + " ".join(f"{r.get(c, 0):{w}d}" for c, w in zip(cols, (5, 6, 6, 7, 6, 5))))
+    sys.exit(0)
+if len(sys.argv) > 2 and sys.argv[2] == "atlas":
+    cols = ("VGPRs", "VGPRs Spill", "SGPRs Spill", "ScratchSize [bytes/lane]", "LDS Size [bytes/block]", "Occupancy [waves/SIMD]")
+    print(f"{'kernel':28s} {'VGPRs':>5s} {'vspill':>6s} {'sspill':>6s} {'scratch':>7s} {'LDS':>6s} {'waves':>5s}")
+    for name, r in recs.items():
+        m = re.search(r"\d+(prim_inverse_kernel|atlas_\w+?_kernel|surface_fill_kernel)(ILb([01]))?", name)
+        if m:
+            lab = m.group(1) + ({"0": "<at>", "1": "<atlas>"}.get(m.group(3), ""))
+            print(f"{lab:28s} " + " ".join(f"{r.get(c, 0):{w}d}" for c, w in zip(cols, (5, 6, 6, 7, 6, 5))))
     sys.exit(0)
 QUERIES = {"radiance": ("ray_radiance_kernel", "RayRadiance"), "surface": ("ray_surface_kernel", "RaySurface"),
            "shade": ("surface_shade_kernel", "SurfaceShade")}

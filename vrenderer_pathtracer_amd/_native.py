@@ -67,6 +67,8 @@ _SIGNATURES = {
     "vrhip_trace_surface": (ctypes.c_int, [_ctx, _vp, _vp, ctypes.c_uint32, _vp]),
     "vrhip_shade_surface": (ctypes.c_int, [_ctx, _vp, _vp, _vp, ctypes.c_uint32, ctypes.c_uint32, _vp]),
     "vrhip_camera_rays": (ctypes.c_int, [_ctx, _vp, _vp]),
+    "vrhip_surface_at": (ctypes.c_int, [_ctx, _vp, _vp, ctypes.c_uint32, _vp]),
+    "vrhip_atlas_surface": (ctypes.c_int, [_ctx, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, _vp]),
     "vrhip_denoise": (ctypes.c_int, [_ctx, _vp, _vp, ctypes.c_uint32, ctypes.c_uint32, _vp, _vp]),
     "vrhip_denoise_frame": (ctypes.c_int, [_ctx, _vp, _vp, _vp]),
     "vrhip_flat_trace_rays": (ctypes.c_int, [_f, ctypes.c_size_t, _f, ctypes.c_size_t, _f, _f, _f, ctypes.c_uint32,

@@ -70,6 +70,14 @@ struct ResidentMesh {
     size_t n_bvh = 0, n_slots = 0;                // the reference layout's float4 rows and slots
     uint32_t bvh_nodes = 0;                       // its node count (vrhip_bvh_info)
     uint32_t refit_verts = 0;                     // the device upload's n_verts
+    // what prim_id's values range over: the caller's triangles after a device
+    // build, the flat slots after a host upload
+    uint32_t n_prims = 0;
+    // the inverse of a.prim_id, u32[n_prims]: the lowest compact triangle of each
+    // prim (vr_atlas.hpp launch_prim_inverse).  Built at the first
+    // vrhip_surface_at, gone with the mesh at the next upload; a refit moves no
+    // triangle and keeps it.
+    uint32_t* prim_inv = nullptr;
 
     ResidentMesh() = default;
     ResidentMesh(const ResidentMesh&) = delete;
@@ -80,12 +88,14 @@ struct ResidentMesh {
     {
         dfree(a.bvh); dfree(a.bvh16); dfree(a.verts); dfree(a.tri_e); dfree(a.tpath); dfree(a.normals);
         dfree(a.tangents); dfree(a.uvs); dfree(a.slot_vert); dfree(a.node_level); dfree(a.prim_id); dfree(status);
+        dfree(prim_inv);
     }
     bool loaded() const { return a.bvh != nullptr; }
     void swap(ResidentMesh& o)
     {
         std::swap(a, o.a); std::swap(status, o.status); std::swap(n_bvh, o.n_bvh); std::swap(n_slots, o.n_slots);
         std::swap(bvh_nodes, o.bvh_nodes); std::swap(refit_verts, o.refit_verts);
+        std::swap(n_prims, o.n_prims); std::swap(prim_inv, o.prim_inv);
     }
     // arrays for max_nodes nodes and n_refs compact triangles (every array at
     // least 16 bytes) into an empty mesh; with_refit_data: slot_vert,
@@ -212,6 +222,9 @@ struct vrhip_ctx {
     // guide records, colour plane and camera rays
     vr4* dn_planes = nullptr; size_t dn_cells = 0;
     uint8_t* dn_frame = nullptr; size_t dn_frame_cells = 0;
+    // vrhip_atlas_surface scratch, grown on demand and kept: the cell planes
+    // and the queue of large triangles (vr_atlas.hpp atlas_scratch_bytes)
+    uint8_t* atlas_scratch = nullptr; size_t atlas_bytes = 0;
     // GL interop (colour, depth textures registered by the display host)
     hipGraphicsResource_t gl_res[2] = { nullptr, nullptr };
     // render service (vrhip_set_service): a session of launches on one

@@ -16,6 +16,36 @@ __device__ __forceinline__ vr_u32x4 surface_row(const vr4& v, float w)
     return vr_u32x4{ __float_as_uint(v.x), __float_as_uint(v.y), __float_as_uint(v.z), __float_as_uint(w) };
 }
 
+// The interpolated texture coordinates of a mesh hit of the triangle at compact
+// slot a: fill_hit's interpolated uv, the same operations on the same operands.
+__device__ __forceinline__ void surface_mesh_uv(const RenderParams& p, int a, float bu, float bv, float& tu, float& tv)
+{
+    const float b0 = 1.f - bu - bv;
+    const vr2 uv0 = p.uvs[a], uv1 = p.uvs[a + 1], uv2 = p.uvs[a + 2];
+    tu = (b0 * uv0.x + bu * uv1.x) + bv * uv2.x;
+    tv = (b0 * uv0.y + bu * uv1.y) + bv * uv2.y;
+}
+
+// The seven rows of a hit's record (vrhip_surface_hit), and row 0 of a miss,
+// whose other rows are zero: the one place the layout is written, for the ray
+// query below and the ray-less ones (vr_atlas.hip).
+__device__ __forceinline__ void surface_hit_rows(float t, uint32_t kind, uint32_t prim, const Hit& h, float bu, float bv,
+                                                 float tu, float tv, vr_u32x4& w0, vr_u32x4& w1, vr_u32x4& w2,
+                                                 vr_u32x4& w3, vr_u32x4& w4, vr_u32x4& w5, vr_u32x4& w6)
+{
+    w0 = vr_u32x4{ __float_as_uint(t), kind, prim, h.type };
+    w1 = surface_row(h.hp, bu);
+    w2 = surface_row(h.n, bv);
+    w3 = surface_row(h.tan, 0.f);
+    w4 = surface_row(h.col, tu);
+    w5 = surface_row(h.spec, tv);
+    w6 = surface_row(h.em, 0.f);
+}
+__device__ __forceinline__ vr_u32x4 surface_miss_row()
+{
+    return vr_u32x4{ __float_as_uint(kRayNoHit), (uint32_t)HK_NONE, kRayMiss, 0u };
+}
+
 // One ray per lane, in ray_radiance_kernel's shape: a block fills its node
 // cache once, then each of its waves takes 64-ray chunks in a grid-stride loop
 // over at most one resident set of blocks.  Lanes past the last ray and lanes
@@ -65,21 +95,11 @@ ray_surface_kernel(const RenderParams p, const RaySurface q)
                     const int a = hr.idx;
                     prim = q.prim_id[a / 3];
                     bu = hr.bu; bv = hr.bv;
-                    // fill_hit's interpolated uv, the same operations on the same operands
-                    const float b0 = 1.f - hr.bu - hr.bv;
-                    const vr2 uv0 = p.uvs[a], uv1 = p.uvs[a + 1], uv2 = p.uvs[a + 2];
-                    tu = (b0 * uv0.x + hr.bu * uv1.x) + hr.bv * uv2.x;
-                    tv = (b0 * uv0.y + hr.bu * uv1.y) + hr.bv * uv2.y;
+                    surface_mesh_uv(p, a, bu, bv, tu, tv);
                 }
-                w0 = vr_u32x4{ __float_as_uint(hr.t), (uint32_t)hr.kind, prim, h.type };
-                w1 = surface_row(h.hp, bu);
-                w2 = surface_row(h.n, bv);
-                w3 = surface_row(h.tan, 0.f);
-                w4 = surface_row(h.col, tu);
-                w5 = surface_row(h.spec, tv);
-                w6 = surface_row(h.em, 0.f);
+                surface_hit_rows(hr.t, (uint32_t)hr.kind, prim, h, bu, bv, tu, tv, w0, w1, w2, w3, w4, w5, w6);
             } else {
-                w0 = vr_u32x4{ __float_as_uint(kRayNoHit), (uint32_t)HK_NONE, kRayMiss, 0u };
+                w0 = surface_miss_row();
             }
         }
         vr_u32x4* rec = reinterpret_cast<vr_u32x4*>(q.hits + i);     // seven 16-B stores per ray

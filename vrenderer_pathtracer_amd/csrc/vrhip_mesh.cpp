@@ -42,6 +42,7 @@ int one_upload_mesh(vrhip_ctx* c, const vr::DeviceMesh& dm, uint32_t depth, uint
     HIP_TRY(hipStreamSynchronize(c->stream));
     m.a.n_nodes = n_nodes; m.a.n_refs = n_refs; m.a.depth = depth;
     m.n_bvh = n_bvh_f4; m.n_slots = n_slots; m.bvh_nodes = nodes;
+    m.n_prims = (uint32_t)n_slots;                // prim_id holds flat slots
     c->mesh.swap(m);
     return VRHIP_OK;
 }
@@ -174,6 +175,7 @@ int vrhip_upload_mesh_device_ex(vrhip_ctx* c, const float* d_positions, const fl
     m.a.n_nodes = st.nodes; m.a.n_refs = sh.n_refs; m.a.depth = st.depth;
     m.n_bvh = 4 * (size_t)st.nodes; m.n_slots = st.slots; m.bvh_nodes = st.nodes;
     m.refit_verts = n_verts;
+    m.n_prims = n_tris;
     c->mesh.swap(m);
     return VRHIP_OK;
 }

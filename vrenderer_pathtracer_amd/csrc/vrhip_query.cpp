@@ -5,12 +5,16 @@
 // (vrhip_trace_surface, vr_surface.hip), what light leaves a surface record the
 // caller supplies (vrhip_shade_surface, vr_shade.hip), and the current camera's
 // rays to feed them (vrhip_camera_rays), and the edge-avoiding filter that turns noisy radiance and the surface
-// query's records into an image (vrhip_denoise, vrhip_denoise_frame, vr_denoise.hip).  All read the scene
+// query's records into an image (vrhip_denoise, vrhip_denoise_frame, vr_denoise.hip),
+// and the records that need no ray: at points of the resident mesh
+// (vrhip_surface_at) and at the texels of a lightmap atlas of its uvs
+// (vrhip_atlas_surface, vr_atlas.hip).  All read the scene
 // only: the accumulation, the images and the frame counter stay as they are.
 #include <cstddef>
 #include <cmath>
 #include <cstring>
 
+#include "vr_atlas.hpp"
 #include "vr_ctx.hpp"
 #include "vr_denoise.hpp"
 #include "vr_radiance.hpp"
@@ -291,6 +295,93 @@ int vrhip_denoise_frame(vrhip_ctx* c, const vrhip_denoise_params* dp, float* d_o
     }
     const int e = vr::launch_denoise(q, c->stream);
     if (e) return fail(VRHIP_ERR_HIP, std::string("denoise frame: ") + hipGetErrorString((hipError_t)e));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return svc_verify(c);
+}
+
+// Grows the atlas scratch to `bytes` (the new buffer before the old one goes,
+// as denoise_scratch).
+static int atlas_scratch(vrhip_ctx* c, size_t bytes)
+{
+    if (c->atlas_bytes >= bytes) return VRHIP_OK;
+    void* raw = nullptr;
+    if (hipMalloc(&raw, bytes) != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(VRHIP_ERR_NOMEM, "atlas scratch: " + std::to_string(bytes) + " bytes");
+    }
+    if (c->atlas_scratch) {
+        (void)hipStreamSynchronize(c->stream);
+        (void)hipFree((void*)c->atlas_scratch);
+    }
+    c->atlas_scratch = (uint8_t*)raw; c->atlas_bytes = bytes;
+    return VRHIP_OK;
+}
+
+// The record at (prim, u, v) of the resident mesh: vrhip_trace_surface's scene
+// and record with no ray.  The inverse of prim_id is built here at first use
+// and stays with the mesh (vr_ctx.hpp ResidentMesh).
+int vrhip_surface_at(vrhip_ctx* c, const uint32_t* d_prims, const float* d_bary, uint32_t n, vrhip_surface_hit* d_hits)
+{
+    if (!c) return fail(VRHIP_ERR_INVALID, "null ctx");
+    if (n > 0 && (!d_prims || !d_bary || !d_hits)) return fail(VRHIP_ERR_INVALID, "null prim, barycentric or hit array");
+    if (((uintptr_t)d_hits & 15u) != 0u) return fail(VRHIP_ERR_INVALID, "d_hits is not 16-byte aligned");
+    if (!c->group.empty()) return refuse_multi(c, "vrhip_surface_at");
+    if (!c->mesh.loaded()) return fail(VRHIP_ERR_INVALID, "no mesh loaded");
+    if (n == 0) return VRHIP_OK;
+    int rc = set_device(c); if (rc) return rc;
+    if ((rc = svc_close(c)) != VRHIP_OK) return rc;
+    ResidentMesh& m = c->mesh;
+    (void)hipGetLastError();            // the launches below report their own errors only
+    if (!m.prim_inv) {
+        uint32_t* inv = nullptr;
+        if (hipMalloc((void**)&inv, m.n_prims ? (size_t)m.n_prims * sizeof(uint32_t) : 16) != hipSuccess) {
+            (void)hipGetLastError();
+            return fail(VRHIP_ERR_NOMEM, "prim inverse: " + std::to_string((size_t)m.n_prims * sizeof(uint32_t)) + " bytes");
+        }
+        const int e = vr::launch_prim_inverse(m.a.prim_id, m.a.n_refs, inv, m.n_prims, c->stream);
+        if (e) {
+            (void)hipStreamSynchronize(c->stream);
+            (void)hipFree(inv);
+            return fail(VRHIP_ERR_HIP, std::string("prim inverse: ") + hipGetErrorString((hipError_t)e));
+        }
+        m.prim_inv = inv;
+    }
+    vr::RenderParams p;
+    std::memset(&p, 0, sizeof(p));
+    scene_params(c, p);
+    const vr::SurfaceAt q{ d_prims, d_bary, n, m.prim_inv, m.n_prims, (vr::SurfaceHit*)d_hits };
+    const int e = vr::launch_surface_at(p, q, c->stream);
+    if (e) return fail(VRHIP_ERR_HIP, std::string("surface at: ") + hipGetErrorString((hipError_t)e));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return svc_verify(c);
+}
+
+// The records of a width x height atlas of the resident mesh's uvs
+// (include/vrhip.h has the definition; the kernels: vr_atlas.hip).
+int vrhip_atlas_surface(vrhip_ctx* c, uint32_t width, uint32_t height, uint32_t gutter, vrhip_surface_hit* d_hits)
+{
+    if (!c) return fail(VRHIP_ERR_INVALID, "null ctx");
+    if (!d_hits) return fail(VRHIP_ERR_INVALID, "null hit array");
+    if (((uintptr_t)d_hits & 15u) != 0u) return fail(VRHIP_ERR_INVALID, "d_hits is not 16-byte aligned");
+    if (width == 0u || height == 0u || width > vr::kAtlasMaxSide || height > vr::kAtlasMaxSide ||
+        (uint64_t)width * height > vr::kAtlasMaxTexels)
+        return fail(VRHIP_ERR_INVALID, "the atlas is " + std::to_string(width) + " x " + std::to_string(height) +
+                                           " (1 to 16384 a side, 2^26 texels at most)");
+    if (gutter > vr::kAtlasMaxGutter)
+        return fail(VRHIP_ERR_INVALID, "gutter is " + std::to_string(gutter) + " (0 to " + std::to_string(vr::kAtlasMaxGutter) + ")");
+    if (!c->group.empty()) return refuse_multi(c, "vrhip_atlas_surface");
+    if (!c->mesh.loaded()) return fail(VRHIP_ERR_INVALID, "no mesh loaded");
+    int rc = set_device(c); if (rc) return rc;
+    if ((rc = svc_close(c)) != VRHIP_OK) return rc;
+    const uint64_t n = (uint64_t)width * height;
+    if ((rc = atlas_scratch(c, vr::atlas_scratch_bytes(n, c->mesh.a.n_refs))) != VRHIP_OK) return rc;
+    vr::RenderParams p;
+    std::memset(&p, 0, sizeof(p));
+    scene_params(c, p);
+    const vr::Atlas q{ width, height, gutter, c->mesh.a.prim_id, c->atlas_scratch, (vr::SurfaceHit*)d_hits };
+    (void)hipGetLastError();            // the launches below report their own errors only
+    const int e = vr::launch_atlas_surface(p, q, c->cu_count, c->stream);
+    if (e) return fail(VRHIP_ERR_HIP, std::string("atlas surface: ") + hipGetErrorString((hipError_t)e));
     HIP_TRY(hipStreamSynchronize(c->stream));
     return svc_verify(c);
 }

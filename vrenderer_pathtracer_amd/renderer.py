@@ -454,10 +454,81 @@ class VRendererHIP:
         torch.cuda.current_stream(dev).synchronize()
         check(self._lib.vrhip_trace_surface(self._ctx, p_o, p_d, n, ctypes.c_void_p(rec.data_ptr())),
               "vrhip_trace_surface")
+        return self._surface_dict(rec)
+
+    @staticmethod
+    def _surface_dict(rec) -> dict:
+        """The views of an (N,28) float32 record tensor that traceSurface,
+        surfaceAt and atlasRecords return."""
+        import torch
         words = rec.view(torch.int32)
         return {"record": rec, "t": rec[:, 0], "kind": words[:, 1], "prim": words[:, 2], "type": words[:, 3],
                 "position": rec[:, 4:7], "normal": rec[:, 8:11], "tangent": rec[:, 12:15], "color": rec[:, 16:19],
                 "specular": rec[:, 20:23], "emission": rec[:, 24:27], "bary": rec[:, 7:12:4], "uv": rec[:, 19:24:4]}
+
+    def surfaceAt(self, prims, bary) -> dict:
+        """The surface records at points of the resident mesh, with no ray
+        (vrhip_surface_at): what traceSurface would return for a hit of
+        triangle prims[i] at barycentrics bary[i] = (u, v).  prims: (N,) int32,
+        uint32 or int64 torch tensor on the renderer's GPU, the triangle as
+        traceRays names it (the row of initMeshDevice's tris, or, for a mesh
+        from initMesh, the slot of its first vertex in the flattened verts);
+        int64 is narrowed here, a value outside 0 .. 2^32 - 2 naming no
+        triangle.  bary: (N,2) float32, used as given (not clamped).  Returns
+        traceSurface's dict with t = 0 and position the barycentric
+        interpolation of the vertices; the maps and the BRDF view apply as
+        render() would apply them now, the Cornell box and the example sphere
+        play no part.  An entry whose prim names no triangle or whose u or v is
+        not finite gives 28 zero words.  ValueError for a wrong device, dtype,
+        shape or layout.  Synchronises torch's current stream first; the query
+        runs on the renderer's own stream and has finished on return."""
+        import torch
+        self._need_ctx()
+        dev = self._torch_device()
+        int_types = tuple(t for t in (torch.int32, getattr(torch, "uint32", None)) if t is not None)
+        if isinstance(prims, torch.Tensor) and prims.dtype == torch.int64:
+            ok = (prims >= 0) & (prims < 0xFFFFFFFF)
+            prims = torch.where(ok, prims, torch.full_like(prims, 0xFFFFFFFF)).to(torch.int32)
+        p_p = self._tensor_ptr("prims", prims, None, int_types)
+        if p_p is None:
+            raise ValueError("prims and bary are required")
+        n = int(prims.shape[0])
+        p_b = self._tensor_ptr("bary", bary, 2, (torch.float32,), n)
+        if p_b is None:
+            raise ValueError("prims and bary are required")
+        rec = torch.empty((n, 28), dtype=torch.float32, device=f"cuda:{dev}")
+        torch.cuda.current_stream(dev).synchronize()
+        check(self._lib.vrhip_surface_at(self._ctx, p_p, p_b, n, ctypes.c_void_p(rec.data_ptr())), "vrhip_surface_at")
+        return self._surface_dict(rec)
+
+    def atlasRecords(self, width: int, height: int, gutter: int = 0) -> dict:
+        """The surface records of a width x height lightmap atlas of the
+        resident mesh's uvs (vrhip_atlas_surface; the definition:
+        include/vrhip.h): texel (x, y), record y * width + x, holds the record
+        of the point of the mesh whose uv is the texel's centre -- the texel
+        render() fetches for that uv once the baked map is loaded with
+        loadTexture.  Where several triangles cover a centre the smallest prim
+        wins; an uncovered texel is a miss (kind 0, t = 1e20).  gutter (0 to
+        64): dilation passes that give an uncovered texel the record of its
+        first covered 8-neighbour, with t the pass that reached it; one pass is
+        what a bake needs against black seams.  Returns traceSurface's dict,
+        (width * height, 28); feed its "record" to shadeSurface and denoise.
+        width, height 1 to 16384, at most 2^26 texels.  Synchronises torch's
+        current stream first; the query runs on the renderer's own stream and
+        has finished on return."""
+        import torch
+        self._need_ctx()
+        dev = self._torch_device()
+        vals = (width, height, gutter)
+        if any(int(v) != v or not 0 <= int(v) < 2**32 for v in vals):
+            raise ValueError("width, height and gutter are non-negative integers")
+        w, h = int(width), int(height)
+        n = w * h if w <= 16384 and h <= 16384 and w * h <= 2**26 else 1     # the library refuses the size
+        rec = torch.empty((max(n, 1), 28), dtype=torch.float32, device=f"cuda:{dev}")
+        torch.cuda.current_stream(dev).synchronize()
+        check(self._lib.vrhip_atlas_surface(self._ctx, w, h, int(gutter), ctypes.c_void_p(rec.data_ptr())),
+              "vrhip_atlas_surface")
+        return self._surface_dict(rec)
 
     def shadeSurface(self, hits, dirs, seeds=None, samples: int = 2):
         """What would the renderer show for these surfaces, seen along these

@@ -85,6 +85,30 @@ def torus_knot(nu: int = 100, nv: int = 50, p: int = 2, q: int = 3, tube: float 
                 tris=tris.astype(np.uint32))
 
 
+def torus_knot_unwrapped(nu: int = 100, nv: int = 50, margin: float = 0.0, p: int = 2, q: int = 3, tube: float = 5.0,
+                         scale: float = 15.0) -> dict:
+    """torus_knot's tube with a UV unwrap a lightmap can be baked into: the
+    vertices of the two seams are duplicated ((nu+1)*(nv+1) vertices, vertex
+    (i, j) a copy of torus_knot's (i % nu, j % nv)) and the uvs are margin +
+    (1 - 2*margin) * (i/nu, j/nv), so no triangle wraps and the chart fills
+    [margin, 1 - margin]^2.  Same triangles in the same order and winding:
+    triangle k is torus_knot's triangle k."""
+    base = torus_knot(nu, nv, p, q, tube, scale)
+    I, J = np.meshgrid(np.arange(nu + 1), np.arange(nv + 1), indexing="ij")
+    src = ((I % nu) * nv + (J % nv)).reshape(-1)
+    uu = margin + (1.0 - 2.0 * margin) * (I.astype(np.float64) / nu)
+    vv = margin + (1.0 - 2.0 * margin) * (J.astype(np.float64) / nv)
+    idx = lambda i, j: i * (nv + 1) + j
+    I, J = np.meshgrid(np.arange(nu), np.arange(nv), indexing="ij")
+    a, b, c, d = idx(I, J), idx(I + 1, J), idx(I + 1, J + 1), idx(I, J + 1)
+    tris = np.stack([np.stack([a, b, c], -1), np.stack([a, c, d], -1)], 2).reshape(-1, 3)
+    if (src[tris[0]] != base["tris"][0]).any():          # torus_knot flipped its winding
+        tris = tris[:, [0, 2, 1]]
+    assert (src[tris] == base["tris"]).all()
+    return dict(positions=base["positions"][src], normals=base["normals"][src], tangents=base["tangents"][src],
+                uvs=np.stack([uu, vv], -1).reshape(-1, 2).astype(np.float32), tris=tris.astype(np.uint32))
+
+
 def procedural_hdr(w: int = 2048, h: int = 1024, seed: int = 7) -> np.ndarray:
     """Equirect environment (rows = acos(dir.y)/pi, cols = atan2(x,z)/2pi as
     sampled at PathTracer.cu:636-643): sky gradient, ground, a sun disc and
