@@ -968,9 +968,38 @@ int vrhip_microbench_vmem(int device, uint32_t width_bytes, uint32_t distinct, d
 int vrhip_debug_counters(vrhip_ctx *ctx, uint64_t out[16], int reset);
 /* Depth of the uploaded BVH and the traversal stack size in use. */
 int vrhip_bvh_info(vrhip_ctx *ctx, uint32_t *depth, uint32_t *n_nodes, uint32_t *n_slots);
-/* Evaluate the device libm on n inputs (test hook: 0 sin, 1 cos, 2 acos,
- * 3 atan2, 4 pow, 5 fmin, 6 fmax, 7 f2i); a,b,out host arrays of n floats. */
+/* Evaluate the device libm on n inputs (test hook); a, b, out host arrays of n
+ * floats (b is read only by the binary functions but must not be NULL).  fn:
+ *    0 sin(a)   1 cos(a)   2 acos(a)   3 atan2(a, b)   4 pow(a, b)
+ *    5 fmin(a, b)   6 fmax(a, b)
+ *    7 f2i(a): float -> int, truncating, saturating, NaN -> 0; the int's bits
+ *    8 d2i((double)a * (double)b): the same from double; the int's bits
+ *    9 f2u8(a): the colour byte (truncate, clamp to [0, 255], NaN -> 0) as a
+ *      float value
+ *   10 sqrt_exact(a)   11 inv_sqrt_exact(a): the path kernels' sqrtf(a) and
+ *      1.0f / sqrtf(a), which take a short sequence when every lane of the
+ *      wave is inside its exact range and the IEEE expansion otherwise
+ *   any other value writes 0.
+ * fn | 0x100 (fn 0..4) runs the same function as compiled in the other of the
+ * two constant forms of the device libm: the one the sphere-only kernels use
+ * (constants the compiler may hoist) instead of the one the mesh kernels use
+ * (constants materialised at each use); VRHIP_ERR_INVALID for fn > 4.
+ * Lane mapping: element i is thread i of a one-dimensional grid of 256-thread
+ * blocks, so lane i % 64 of wave i / 64; the layout of a therefore decides
+ * which values share a wave in fn 10 and 11, and a last wave of n % 64
+ * elements votes over those lanes only.  n == 0 launches nothing and is
+ * VRHIP_OK.  The device buffers are freed on every return. */
 int vrhip_selftest_math(int device, int fn, const float *a, const float *b, float *out, size_t n);
+/* The BRDF lookup of the shading step (lookupBRDF, PathTracer.cu:519-566) on
+ * n caller-supplied frames (test hook).  table: a planar MERL table as
+ * vrhip_upload_brdf takes it, n_floats == 3*90*90*180 (anything else is
+ * VRHIP_ERR_INVALID), interleaved and uploaded as vrhip_upload_brdf does.
+ * frames: 16 n floats, per frame the float4s refl (the sampled direction),
+ * cur (the arriving ray's direction), normal, tangent; nothing is normalised
+ * or checked: the three table indices are clamped, so no input reads outside
+ * the table.  out: 4 n floats, the lookup's float4 (r/1500, g*1.15/1500,
+ * b*1.66/1500, 0) per frame, before the shading step's max with 0. */
+int vrhip_selftest_brdf(int device, const float *table, size_t n_floats, const float *frames, size_t n, float *out);
 /* The device BVH builder's outward fp32 -> fp16 box rounding on n host
  * floats (test hook): down[i] rounded toward -inf, up[i] toward +inf, as
  * binary16 bit patterns. */

@@ -56,6 +56,7 @@ void vro_p_sincosf(float x, float *s, float *c)
     pc = fma(pc, z, -0.5);
     double cd = fma(z, pc, 1.0);
     float sp = (float)sd, cp = (float)cd;
+    if (x == 0.0f) sp = x;                 /* sin(-0) = -0: the reduction's +0 + -0 loses the sign */
     int q = ((int)k) & 3;
     if (q == 0)      { *s = sp;  *c = cp;  }
     else if (q == 1) { *s = cp;  *c = -sp; }
@@ -272,10 +273,11 @@ float vro_p_powf(float x, float y)
         if (t == y) { yint = 1; yodd = (((int64_t)t) & 1) != 0; }
     }
     int xneg = (ux >> 31) != 0;
-    if (xneg && ax_b != 0 && !yint) return u2f(0x7fc00000u);
     float sign = (xneg && yodd) ? -1.0f : 1.0f;
-    if (ax_b == 0) return (uy >> 31) ? sign * u2f(0x7f800000u) : sign * 0.0f;
+    /* -inf is no negative finite base: pow(-inf, y) is 0 or inf for every y, as pow(-0, y) is (C99 F.9.4.4) */
     if (ax_b == 0x7f800000u) return (uy >> 31) ? sign * 0.0f : sign * u2f(0x7f800000u);
+    if (xneg && ax_b != 0 && !yint) return u2f(0x7fc00000u);
+    if (ax_b == 0) return (uy >> 31) ? sign * u2f(0x7f800000u) : sign * 0.0f;
     if (ay_b == 0x7f800000u) {
         if (ax == 1.0f) return 1.0f;
         int big = ax > 1.0f;

@@ -121,6 +121,7 @@ _SIGNATURES = {
     "vrhip_set_service_budget": (ctypes.c_int, [_ctx, ctypes.c_size_t]),
     "vrhip_bvh_info": (ctypes.c_int, [_ctx, _u32, _u32, _u32]),
     "vrhip_selftest_math": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, _f, _f, _f, ctypes.c_size_t]),
+    "vrhip_selftest_brdf": (ctypes.c_int, [ctypes.c_int, _f, ctypes.c_size_t, _f, ctypes.c_size_t, _f]),
     "vrhip_selftest_half_box": (ctypes.c_int, [ctypes.c_int, _f, ctypes.c_size_t, _u16, _u16]),
     "vrhip_selftest_rcp": (ctypes.c_int, [ctypes.c_int, ctypes.c_uint32, ctypes.c_uint32,
                                           ctypes.POINTER(ctypes.c_uint64), _u32]),

@@ -22,6 +22,7 @@ SOURCES = ["vr_spec_generic.hip", "vr_cls_cornell_mesh.hip", "vr_cls_hdri_mesh.h
            "vr_radiance_cornell_mesh.hip", "vr_radiance_hdri_mesh.hip", "vr_radiance.hip", "vr_radiance_sphere.hip",
            "vr_surface_cornell_mesh.hip", "vr_surface_hdri_mesh.hip", "vr_surface.hip", "vr_surface_sphere.hip",
            "vr_shade_cornell_mesh.hip", "vr_shade_hdri_mesh.hip", "vr_shade.hip", "vr_shade_sphere.hip", "vr_denoise.hip", "vr_atlas.hip",
+           "vr_selftest_hoisted.hip",
            "vrhip_scene.cpp", "vrhip_mesh.cpp", "vrhip_query.cpp", "vrhip_service.cpp", "vrhip_render.cpp", "vrhip_multi.cpp",
            "vrhip_selftest.cpp", "vr_mesh_layout.cpp", "vr_raycast.cpp", "vr_bvh.cpp", "vr_exr.cpp", "vr_merl.cpp"]
 HEADERS = ["vr_params.hpp", "vr_math.hpp", "vr_bvh.hpp", "vr_exr.hpp", "vr_merl.hpp", "vr_kernel.hpp", "vr_devmesh.hpp", "vr_devmesh_dev.hpp", "vr_devbvh.hpp", "vr_devsah.hpp", "vr_refit.hpp", "vr_rayquery.hpp",

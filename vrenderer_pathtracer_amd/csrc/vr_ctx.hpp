@@ -355,6 +355,8 @@ int one_upload_hdr(vrhip_ctx* c, const float* rgba, uint32_t w, uint32_t h);
 int one_upload_hdr_half(vrhip_ctx* c, const uint16_t* rgba_half, uint32_t w, uint32_t h);
 int one_upload_texture(vrhip_ctx* c, int type, const float* rgba, uint32_t w, uint32_t h);
 int one_upload_brdf(vrhip_ctx* c, const float* table, size_t n_floats);
+// the device layout of a planar R,G,B MERL table of 3*1458000 floats: entry i's three channels adjacent
+std::vector<float> brdf_interleaved(const float* table);
 // vrhip_multi.cpp
 int refuse_multi(vrhip_ctx* c, const char* what);
 int multi_gather(vrhip_ctx* c, int what);

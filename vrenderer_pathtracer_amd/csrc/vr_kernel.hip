@@ -221,6 +221,12 @@ __global__ void unpack_ranks_kernel(const uint32_t* __restrict__ src, uint32_t* 
     }
 }
 
+// vrhip_selftest_math: element i is thread i of a one-dimensional grid of
+// 256-thread blocks, so lane i % 64 of wave i / 64 -- the input array's layout
+// decides what each wave of sqrt_exact / inv_sqrt_exact (fn 10, 11) votes on.
+// The tail test stays ahead of the switch: a partial last wave ballots only
+// its live lanes.  (The sin/cos/acos/atan2/pow cases in the other constant
+// form of vr_math.hpp: vr_selftest_hoisted.hip, fn | kSelftestHoisted.)
 __global__ void selftest_math_kernel(int fn, const float* a, const float* b, float* out, size_t n)
 {
     const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -235,9 +241,32 @@ __global__ void selftest_math_kernel(int fn, const float* a, const float* b, flo
     case 5: r = __builtin_fminf(a[i], b[i]); break;
     case 6: r = __builtin_fmaxf(a[i], b[i]); break;
     case 7: r = __int_as_float(f2i(a[i])); break;
+    case 8: r = __int_as_float(d2i((double)a[i] * (double)b[i])); break;
+    case 9: r = (float)f2u8(a[i]); break;
+    case 10: r = sqrt_exact(a[i]); break;
+    case 11: r = inv_sqrt_exact(a[i]); break;
     default: r = 0.f;
     }
     out[i] = r;
+}
+
+// vrhip_selftest_brdf: lookup_brdf, as the shading step calls it, on n frames
+// (refl, cur, normal, tangent: four float4 each) against a full table in the
+// layout of vrhip_upload_brdf; the index is clamped into the table
+__global__ void selftest_brdf_kernel(const float* T, const vr4* frames, vr4* out, size_t n)
+{
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const vr4* f = frames + 4 * i;
+    out[i] = lookup_brdf(T, f[0], f[1], f[2], f[3]);
+}
+
+int launch_selftest_brdf(const float* T, const vr4* frames, vr4* out, size_t n, void* stream)
+{
+    if (n == 0) return 0;
+    const unsigned blocks = (unsigned)((n + 255) / 256);
+    hipLaunchKernelGGL(selftest_brdf_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, T, frames, out, n);
+    return (int)hipGetLastError();
 }
 
 // Flags outside the five exact specialisations -> their feature class
@@ -530,6 +559,7 @@ int launch_vmem_roof(int width, const uint32_t* tab, uint32_t n_lines, uint32_t 
 int launch_selftest_math(int fn, const float* a, const float* b, float* out, size_t n, void* stream)
 {
     if (n == 0) return 0;
+    if (fn & kSelftestHoisted) return launch_selftest_math_hoisted(fn & ~kSelftestHoisted, a, b, out, n, stream);
     const unsigned blocks = (unsigned)((n + 255) / 256);
     hipLaunchKernelGGL(selftest_math_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, fn, a, b, out, n);
     return (int)hipGetLastError();

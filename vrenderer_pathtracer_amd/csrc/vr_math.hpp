@@ -72,12 +72,14 @@ __device__ __forceinline__ void sincos_p(float x, float* s, float* c)
     pc = __builtin_fma(pc, z, dk(-0.5));
     const double cd = __builtin_fma(z, pc, dk(1.0));
     const float sp = (float)sd, cp = (float)cd;
-    const int q = ((int)k) & 3;
-    float so, co;
-    if (q == 0)      { so = sp;  co = cp;  }
-    else if (q == 1) { so = cp;  co = -sp; }
-    else if (q == 2) { so = -sp; co = -cp; }
-    else             { so = -cp; co = sp;  }
+    const uint32_t q = (uint32_t)(int)k;
+    // sin x, cos x from sin r, cos r by the quadrant: swapped when q is odd, the sine negated in quadrants 2 and 3 and
+    // the cosine in 1 and 2; at x = +-0 (q = 0, sp = +0) the sine takes the sign of x
+    const uint32_t sb = fbits(sp), cb = fbits(cp);
+    const bool odd = (q & 1u) != 0u;
+    const uint32_t zs = x == 0.0f ? fbits(x) : ((q & 2u) << 30);
+    const float so = bitsf((odd ? cb : sb) ^ zs);
+    const float co = bitsf((odd ? sb : cb) ^ (((q + 1u) & 2u) << 30));
     *s = so; *c = co;
 }
 
@@ -261,10 +263,11 @@ __device__ __forceinline__ float pow_p(float x, float y)
         if (t == y) { yint = true; yodd = (((long long)t) & 1) != 0; }
     }
     const bool xneg = (ux >> 31) != 0;
-    if (xneg && axb != 0 && !yint) return bitsf(0x7fc00000u);
     const float sign = (xneg && yodd) ? -1.0f : 1.0f;
-    if (axb == 0) return (uy >> 31) ? sign * bitsf(0x7f800000u) : sign * 0.0f;
+    // -inf is no negative finite base: pow(-inf, y) is 0 or inf for every y, as pow(-0, y) is
     if (axb == 0x7f800000u) return (uy >> 31) ? sign * 0.0f : sign * bitsf(0x7f800000u);
+    if (xneg && axb != 0 && !yint) return bitsf(0x7fc00000u);
+    if (axb == 0) return (uy >> 31) ? sign * bitsf(0x7f800000u) : sign * 0.0f;
     if (ayb == 0x7f800000u) {
         if (ax == 1.0f) return 1.0f;
         const bool big = ax > 1.0f;

@@ -262,7 +262,11 @@ int launch_unpack_ranks(const void* src, void* dst, uint32_t elem_bytes, uint32_
                         uint32_t total_tiles, uint32_t r0, uint32_t nranks, size_t stride_bytes, void* stream);
 int launch_vmem_roof(int width, const uint32_t* tab, uint32_t n_lines, uint32_t distinct, int iters,
                      uint32_t blocks, uint32_t* out, void* stream);
+// fn | kSelftestHoisted: the libm cases (0..4) as compiled with VR_DK_HOISTED (vr_selftest_hoisted.hip)
+constexpr int kSelftestHoisted = 0x100;
 int launch_selftest_math(int fn, const float* a, const float* b, float* out, size_t n, void* stream);
+int launch_selftest_math_hoisted(int fn, const float* a, const float* b, float* out, size_t n, void* stream);
+int launch_selftest_brdf(const float* table, const vr4* frames, vr4* out, size_t n, void* stream);
 int launch_selftest_exact(int fn, uint32_t lo, uint32_t hi, unsigned long long* n_bad, uint32_t* first_bad,
                           const float* tone_t, void* stream);
 // the tonemap threshold table (256 floats; vr_kernel.hpp tone_byte)

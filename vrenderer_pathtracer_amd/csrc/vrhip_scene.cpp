@@ -280,6 +280,15 @@ int one_upload_texture(vrhip_ctx* c, int type, const float* rgba, uint32_t w, ui
     return VRHIP_OK;
 }
 
+std::vector<float> brdf_interleaved(const float* table)
+{
+    const size_t n = 90u * 90u * 360u / 2u;
+    std::vector<float> rgb(3 * n);
+    for (size_t i = 0; i < n; ++i)
+        for (int k = 0; k < 3; ++k) rgb[3 * i + k] = table[k * n + i];
+    return rgb;
+}
+
 int one_upload_brdf(vrhip_ctx* c, const float* table, size_t n_floats)
 {
     const size_t n = 90u * 90u * 360u / 2u;    // BRDF_SAMPLING_RES_* (include/vRenderer.h:23-25)
@@ -287,9 +296,7 @@ int one_upload_brdf(vrhip_ctx* c, const float* table, size_t n_floats)
     int rc = set_device(c); if (rc) return rc;
     // The device copy is interleaved (entry i's three channels adjacent): one
     // lookup touches one cache line instead of three, 5.8 MB apart.
-    std::vector<float> rgb(3 * n);
-    for (size_t i = 0; i < n; ++i)
-        for (int k = 0; k < 3; ++k) rgb[3 * i + k] = table[k * n + i];
+    const std::vector<float> rgb = brdf_interleaved(table);
     if ((rc = upload(c, c->brdf, rgb.data(), 3 * n * sizeof(float)))) return rc;
     HIP_TRY(hipStreamSynchronize(c->stream));
     return VRHIP_OK;

@@ -2,6 +2,7 @@
 // (vrhip_selftest_*, vrhip_microbench_vmem): no context, a device index only.
 #include "vr_ctx.hpp"
 #include "vr_devmesh.hpp"
+#include "vr_merl.hpp"
 
 int vrhip_microbench_vmem(int device, uint32_t width_bytes, uint32_t distinct, double* lane_loads_per_s)
 {
@@ -43,17 +44,38 @@ int vrhip_microbench_vmem(int device, uint32_t width_bytes, uint32_t distinct, d
 int vrhip_selftest_math(int device, int fn, const float* a, const float* b, float* out, size_t n)
 {
     if (!a || !b || !out) return fail(VRHIP_ERR_INVALID, "null argument");
+    if ((fn & vr::kSelftestHoisted) && (fn & ~vr::kSelftestHoisted) > 4)
+        return fail(VRHIP_ERR_INVALID, "the hoisted constant form holds functions 0..4 only");
+    if (n == 0) return VRHIP_OK;                          // nothing to launch
     HIP_TRY(hipSetDevice(device));
-    float *da = nullptr, *db = nullptr, *dout = nullptr;
-    HIP_TRY(hipMalloc((void**)&da, n * 4 + 4));
-    HIP_TRY(hipMalloc((void**)&db, n * 4 + 4));
-    HIP_TRY(hipMalloc((void**)&dout, n * 4 + 4));
-    HIP_TRY(hipMemcpy(da, a, n * 4, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(db, b, n * 4, hipMemcpyHostToDevice));
-    int e = vr::launch_selftest_math(fn, da, db, dout, n, nullptr);
-    if (e) return fail(VRHIP_ERR_HIP, "selftest launch failed");
-    HIP_TRY(hipMemcpy(out, dout, n * 4, hipMemcpyDeviceToHost));
-    (void)hipFree(da); (void)hipFree(db); (void)hipFree(dout);
+    float* d = nullptr;                                   // a, b, out: n floats each
+    HIP_TRY(hipMalloc((void**)&d, 3 * n * 4));
+    hipError_t e = hipMemcpy(d, a, n * 4, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(d + n, b, n * 4, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = (hipError_t)vr::launch_selftest_math(fn, d, d + n, d + 2 * n, n, nullptr);
+    if (e == hipSuccess) e = hipMemcpy(out, d + 2 * n, n * 4, hipMemcpyDeviceToHost);
+    (void)hipFree(d);                                     // on every path
+    if (e != hipSuccess) return fail(VRHIP_ERR_HIP, std::string("math selftest: ") + hipGetErrorString(e));
+    return VRHIP_OK;
+}
+
+int vrhip_selftest_brdf(int device, const float* table, size_t n_floats, const float* frames, size_t n, float* out)
+{
+    if (!table || !frames || !out) return fail(VRHIP_ERR_INVALID, "null argument");
+    if (n_floats != vr::kMerlFloats) return fail(VRHIP_ERR_INVALID, "BRDF table must hold 3*1458000 floats");
+    if (n == 0) return VRHIP_OK;
+    HIP_TRY(hipSetDevice(device));
+    const std::vector<float> rgb = brdf_interleaved(table);
+    float *dT = nullptr, *df = nullptr;                   // df: the frames (16 n floats), then the results (4 n)
+    HIP_TRY(hipMalloc((void**)&dT, n_floats * 4));
+    if (hipMalloc((void**)&df, n * 80) != hipSuccess) { (void)hipFree(dT); return fail(VRHIP_ERR_NOMEM, "selftest buffers"); }
+    hipError_t e = hipMemcpy(dT, rgb.data(), n_floats * 4, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(df, frames, n * 64, hipMemcpyHostToDevice);
+    if (e == hipSuccess)
+        e = (hipError_t)vr::launch_selftest_brdf(dT, (const vr::vr4*)df, (vr::vr4*)(df + 16 * n), n, nullptr);
+    if (e == hipSuccess) e = hipMemcpy(out, df + 16 * n, n * 16, hipMemcpyDeviceToHost);
+    (void)hipFree(dT); (void)hipFree(df);
+    if (e != hipSuccess) return fail(VRHIP_ERR_HIP, std::string("BRDF selftest: ") + hipGetErrorString(e));
     return VRHIP_OK;
 }
 

@@ -1026,11 +1026,25 @@ class VRendererHIP:
 
 
 def selftest_math(fn: int, a, b=None, device: int = 0) -> np.ndarray:
-    """Evaluate the device libm (0 sin, 1 cos, 2 acos, 3 atan2, 4 pow, 5 fmin, 6 fmax, 7 f2i)."""
+    """Evaluate the device libm (0 sin, 1 cos, 2 acos, 3 atan2, 4 pow, 5 fmin, 6 fmax, 7 f2i, 8 d2i(a * b), 9 f2u8,
+    10 sqrt_exact, 11 inv_sqrt_exact; fn | 0x100: functions 0..4 in the sphere kernels' constant form).  Element
+    i runs on lane i % 64 of wave i / 64 (include/vrhip.h)."""
     a = _f32(a).reshape(-1)
     b = _f32(np.zeros_like(a) if b is None else b).reshape(-1)
     out = np.zeros_like(a)
     check(_native.lib().vrhip_selftest_math(device, fn, fptr(a), fptr(b), fptr(out), a.size), "vrhip_selftest_math")
+    return out
+
+
+def selftest_brdf(table, frames, device: int = 0) -> np.ndarray:
+    """The shading step's BRDF lookup on frames [n, 4, 4] (refl, cur, normal,
+    tangent) against a planar MERL table of 3*90*90*180 floats
+    (vrhip_selftest_brdf): [n, 4] float32."""
+    t = _f32(table).reshape(-1)
+    f = _f32(frames).reshape(-1, 16)
+    out = np.zeros((f.shape[0], 4), np.float32)
+    check(_native.lib().vrhip_selftest_brdf(device, fptr(t), t.size, fptr(f), f.shape[0], fptr(out)),
+          "vrhip_selftest_brdf")
     return out
 
 
