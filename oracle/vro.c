@@ -210,6 +210,17 @@ typedef struct {
 
 #define CNT(field, v) do { if (tc->cnt) tc->cnt->field += (v); } while (0)
 
+/* The traversal stack of PathTracer.cu:278 (int traversalStack[64]).  No build
+ * of the oracle defines the two macros below: a push that finds the stack full
+ * is error -3.  tests/stack_driver.c includes this file with a smaller
+ * VRO_STACK_CAPACITY (any int expression up to VRO_STACK_ENTRIES) and
+ * VRO_STACK_DROP, under which such a push is lost instead: the mutants that
+ * show a one-entry error in a kernel's stack would be seen. */
+#define VRO_STACK_ENTRIES 64
+#ifndef VRO_STACK_CAPACITY
+#define VRO_STACK_CAPACITY VRO_STACK_ENTRIES
+#endif
+
 static inline void set_sphere_hit(hit_t *h, const ray_t *r, float t, const sphere_t *s, vf4 spec)
 {
     h->hitPoint = add4(r->o, mul4s(r->d, t));
@@ -361,7 +372,7 @@ static int intersect_scene(tctx *tc, const ray_t *r, hit_t *h)
         }
     } else if (sc->mesh_initialised) {                              /* :269-464 */
         const int Sentinel = 0x76543210;
-        int stack[64];
+        int stack[VRO_STACK_ENTRIES];
         int sp = 0;
         stack[0] = Sentinel;
         int leafAddr = 0;
@@ -402,9 +413,16 @@ static int intersect_scene(tctx *tc, const ray_t *r, hit_t *h)
                     nodeAddr = tc0 ? idx0 : idx1;
                     if (tc0 && tc1) {
                         if (swp) { int tmp = nodeAddr; nodeAddr = idx1; idx1 = tmp; }
-                        if (sp + 1 >= 64) { tc->err = -3; return 0; }
-                        stack[++sp] = idx1;
-                        if (tc->cnt && (uint64_t)sp > tc->cnt->max_stack) tc->cnt->max_stack = (uint64_t)sp;
+                        if (sp + 1 >= VRO_STACK_CAPACITY) {
+#ifdef VRO_STACK_DROP
+                            (void)idx1;                             /* the mutant: the entry is lost */
+#else
+                            tc->err = -3; return 0;
+#endif
+                        } else {
+                            stack[++sp] = idx1;
+                            if (tc->cnt && (uint64_t)sp > tc->cnt->max_stack) tc->cnt->max_stack = (uint64_t)sp;
+                        }
                     }
                 }
                 if (nodeAddr < 0 && leafAddr >= 0) {                /* postpone max 1 */

@@ -120,6 +120,14 @@ def generate(names, check=False):
                     depth, _ = validate_flat(sc["mesh_flat"])
                     assert depth > 15, depth
                     extra["tree_depth"] = int(depth)
+                if rc.CASES[name][1] == "stack":
+                    from vrenderer_pathtracer_amd import validate_flat
+                    depth, _ = validate_flat(sc["mesh_flat"])
+                    assert depth == rc.CASES[name][2]["depth"], depth
+                    extra["tree_depth"] = int(depth)
+                    extra["max_stack"] = po.render(sc, frames=2, times=rc.times_of(name), libm=po.LIBM_PORTABLE,
+                                                   count=True)[3]["max_stack"]
+                    assert extra["max_stack"] == depth, extra        # the oracle's walk fills the stack the reference has
                 times = rc.times_of(name)
                 pa, pr, pd, _ = po.render_reference(builds["ref_portable_zero"], sc, times, d)
                 ga, gr, _, _ = po.render_reference(builds["ref_glibc_zero"], sc, times, d)

@@ -33,6 +33,9 @@ SHADING_CASES = ("S_odd_C3", "S_tall_C3B", "S_tall_C2N", "S_dot_C1T", "S_odd_C4D
 SCALAR_CASES = ("T_2p24p1_C2", "T_2p32m1_C2", "K_skewed_C3", "K_fov_10_C3", "K_up_C3", "F_0_0.5_C3", "F_1_64_C3",
                 "I_16x64_C2")
 
+# the comb of tests/stack_cases.py at the last depth of the 32-entry stack and of the 64-entry one, and its legged kind
+STACK_CASES = (("C2", "comb", 30), ("C3", "comb", 30), ("C2", "comb", 62), ("C3", "comb", 62), ("C2", "legged", 62))
+
 # name -> (family file, recipe, parameters)
 CASES = {
     "C1": ("configs", "config", dict(cfg="C1", frames=3)),
@@ -59,6 +62,8 @@ CASES = {
     **{n: ("shading", "shading", dict(case=n)) for n in SHADING_CASES},
     # time seeds, cameras, Fresnel pairs and an image shape: recipes in tests/launch_scalar_cases.py
     **{n: ("scalars", "scalars", dict(case=n)) for n in SCALAR_CASES},
+    # trees that fill the 32- and the 64-entry stack to the last entry: recipes in tests/stack_cases.py
+    **{f"{cfg}_{tree}{depth}": ("stacks", "stack", dict(cfg=cfg, tree=tree, depth=depth)) for cfg, tree, depth in STACK_CASES},
 }
 # cases in which no primary hit lies farther than the depth byte's range
 # (150 units), so the depth image compares on every pixel
@@ -152,6 +157,9 @@ def make_case(name, stored=None):
     elif recipe == "scalars":
         import launch_scalar_cases
         sc = launch_scalar_cases.ref_scene(p["case"])
+    elif recipe == "stack":
+        import stack_cases
+        sc = stack_cases.scene(stack_cases.tree(p["tree"], p["depth"]), p["cfg"], w, h)
     else:
         raise ValueError(recipe)
     sc["name"] = name
