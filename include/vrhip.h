@@ -580,6 +580,84 @@ int vrhip_atlas_surface(vrhip_ctx *ctx, uint32_t width, uint32_t height, uint32_
 int vrhip_shade_surface(vrhip_ctx *ctx, const vrhip_surface_hit *d_hits /*[n], 16-byte aligned*/,
                         const float *d_dirs /*float[3n]*/, const uint32_t *d_seeds /*uint32[2n]*/,
                         uint32_t n_hits, uint32_t n_samples, float *d_radiance /*float4[n], 16-byte aligned*/);
+/* Probe query (no reference counterpart as a call): radiance from n_probes
+ * points along one shared set of n_dirs directions, projected onto real
+ * spherical harmonics (SH) to band 2 inside the call, and the call that turns
+ * the coefficients back into irradiance at a normal.  The loop of an irradiance
+ * probe grid: vrhip_probe_sh -> vrhip_sh_irradiance.  No buffer of
+ * n_probes * n_dirs elements is allocated; the call's scratch is at most
+ * n_probes * ceil(n_dirs / 64) * 112 bytes.  All arrays are device pointers on
+ * the context's device; d_sh is 16-byte aligned.
+ *   Ray (i, k): exactly the ray vrhip_trace_radiance would trace with origin
+ *     d_points[3i..], direction d_dirs[3k..], the seed pair
+ *     (d_probe_seeds[2i] ^ d_dir_seeds[2k],
+ *      d_probe_seeds[2i+1] ^ d_dir_seeds[2k+1]) and n_samples paths, one after
+ *     the other.  Its validity rule, normalisation, shared escape under an
+ *     HDRI and path-order mean are that query's own, and so are the scene, the
+ *     flag word, the traversal mode, the session handling and the order of
+ *     refusals.  L = the rgb of the record that call would return, d =
+ *     (x, y, z) the normalised direction it traced.  A ray is invalid when the
+ *     point is not finite or the direction fails that query's rule.
+ *   Basis: in fp32, every product and sum rounded on its own, in this order:
+ *       Y0 = 0.282094792f
+ *       Y1 = 0.488602512f*y    Y2 = 0.488602512f*z    Y3 = 0.488602512f*x
+ *       Y4 = 1.09254843f*(x*y) Y5 = 1.09254843f*(y*z)
+ *       Y6 = 0.315391565f*(3.f*(z*z) - 1.f)
+ *       Y7 = 1.09254843f*(x*z) Y8 = 0.546274215f*(x*x - y*y)
+ *   Term: t[j][c] = (w_k * Y_j) * L[c], w_k = d_weights[k] used as given (NaN
+ *     and inf propagate), or 12.566370614f / (float)n_dirs with d_weights
+ *     NULL.  An invalid ray's term is +0.f whatever its weight (not w*Y*0).
+ *   Sum: directions are taken in blocks of VRHIP_PROBE_BLOCK = 64 consecutive
+ *     k.  Slot l of block b holds the term of direction 64b + l, or +0.f
+ *     beyond n_dirs.  The 64 slots are added by the fixed tree
+ *       for s in 32, 16, 8, 4, 2, 1: for l < s: v[l] = v[l] + v[l + s]
+ *     and the block partials v[0] are added in ascending b, starting from
+ *     +0.f.  The order does not depend on the grid, on residency or on how the
+ *     work is split over launches; there are no floating-point atomics.
+ *   Record: VRHIP_PROBE_WORDS = 28 words per probe.  Word 3j + c is coefficient
+ *     j of channel c; word 27 is a uint32, the number of valid rays of the
+ *     probe.
+ *   Range: as vrhip_trace_radiance.  Parity with the CPU oracle is pinned for
+ *     points at scene scale (tests/test_gpu_probe.py).
+ *   Cost: one wave per (probe, block), lane l tracing direction 64b + l; the
+ *     lanes of a block share a wave, so directions that are close together in
+ *     a block walk the scene together.
+ * 1 <= n_samples <= 4096, 1 <= n_dirs <= 65536.  The work runs on the context
+ * stream and the call returns when it has finished.  It closes a render-service
+ * session and touches nothing resident.  n_probes == 0: VRHIP_OK, nothing
+ * written.  VRHIP_ERR_INVALID, before any device call, for a null ctx, a null
+ * array other than d_weights with n_probes > 0, a misaligned d_sh, n_samples or
+ * n_dirs out of range, and a vrhip_create_multi context.  VRHIP_ERR_NO_ENV in
+ * HDRI mode without an environment map, exactly where vrhip_trace_radiance
+ * returns it.  VRHIP_ERR_NOMEM when the scratch cannot be allocated.  Added
+ * without an ABI version change (ABI 6 gained this symbol and changed no
+ * other). */
+#define VRHIP_PROBE_BLOCK 64
+#define VRHIP_PROBE_WORDS 28
+int vrhip_probe_sh(vrhip_ctx *ctx, const float *d_points /*float[3 n_probes]*/,
+                   const float *d_dirs /*float[3 n_dirs], shared by all probes*/,
+                   const float *d_weights /*float[n_dirs] or NULL*/,
+                   const uint32_t *d_probe_seeds /*uint32[2 n_probes]*/, const uint32_t *d_dir_seeds /*uint32[2 n_dirs]*/,
+                   uint32_t n_probes, uint32_t n_dirs, uint32_t n_samples,
+                   float *d_sh /*float4[7 n_probes] = 28 words per probe, 16-byte aligned*/);
+/* Irradiance at a normal from the records of vrhip_probe_sh; needs no scene and
+ * no mesh.  Output q takes record p = d_index ? d_index[q] : q of the m records
+ * and the normal (x, y, z) = d_normals[3q..], used as given (not normalised, as
+ * vrhip_shade_surface treats normals).  With Y0..Y8 the basis above on the
+ * normal, A0 = 3.14159274f, A1 = 2.09439516f, A2 = 0.785398185f (the
+ * clamped-cosine lobe of Ramamoorthi and Hanrahan, "An Efficient Representation
+ * for Irradiance Environment Maps", SIGGRAPH 2001) and A(j) = A0 for j = 0, A1
+ * for j = 1..3, A2 for j = 4..8, per channel c in fp32, every product and sum
+ * rounded on its own, left to right in j:
+ *   E[c] = ((A(0)*(sh[0][c]*Y0) + A(1)*(sh[1][c]*Y1)) + ...) + A(8)*(sh[8][c]*Y8)
+ * out = (E.r, E.g, E.b, 0); d_index[q] >= m gives (0, 0, 0, 0).  n == 0:
+ * VRHIP_OK, nothing written.  VRHIP_ERR_INVALID, before any device call, for a
+ * null ctx, a null d_sh, d_normals or d_out with n > 0, a misaligned d_out,
+ * d_index NULL with n > 0 and n != m, and a vrhip_create_multi context.  Synchronous;
+ * closes a render-service session.  Added without an ABI version change. */
+int vrhip_sh_irradiance(vrhip_ctx *ctx, const float *d_sh /*28 words per probe, m probes*/, uint32_t m,
+                        const uint32_t *d_index /*uint32[n] or NULL (then n == m, identity)*/,
+                        const float *d_normals /*float[3n]*/, uint32_t n, float *d_out /*float4[n], 16-byte aligned*/);
 /* Edge-avoiding a-trous denoiser (no reference counterpart: the reference shows
  * its accumulation unfiltered; Dammertz et al., "Edge-Avoiding A-Trous Wavelet
  * Transform for fast Global Illumination Filtering", HPG 2010).  The step
@@ -826,7 +904,7 @@ int vrhip_set_overlap(vrhip_ctx *ctx, int mode);
  *   vrhip_gl_present, vrhip_pack_tiles/unpack_tiles, vrhip_last_kernel_ms,
  *   vrhip_kernel_stats, vrhip_debug_counters, vrhip_set_camera, vrhip_clear,
  *   every upload (vrhip_upload_mesh_device too), vrhip_refit_mesh_device,
- *   vrhip_bvh_sah_cost, vrhip_export_mesh_flat, vrhip_trace_rays, vrhip_trace_radiance, vrhip_trace_surface, vrhip_shade_surface, vrhip_camera_rays, vrhip_surface_at, vrhip_atlas_surface, vrhip_denoise, vrhip_denoise_frame, vrhip_set_stream, vrhip_set_tiling, vrhip_set_service
+ *   vrhip_bvh_sah_cost, vrhip_export_mesh_flat, vrhip_trace_rays, vrhip_trace_radiance, vrhip_trace_surface, vrhip_shade_surface, vrhip_probe_sh, vrhip_sh_irradiance, vrhip_camera_rays, vrhip_surface_at, vrhip_atlas_surface, vrhip_denoise, vrhip_denoise_frame, vrhip_set_stream, vrhip_set_tiling, vrhip_set_service
  *   (and its timing / budget hooks), vrhip_comm_init/destroy, vrhip_destroy,
  *   the counting renders, and a vrhip_render that does not fit the session.
  *   Calls that do NOT close it: the flag setters (Cornell box, example sphere,

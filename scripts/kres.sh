@@ -11,6 +11,10 @@
 # With `shade`: every instantiation of the surface-record radiance kernel
 # (vr_shade*.hip) in the same table:
 #   bash scripts/kres.sh variants/<name>.log shade
+# With `probe`: every instantiation of the probe kernel (vr_probe*.hip) beside
+# ray_radiance_kernel of the same feature set and stack size, and the two
+# small kernels of vr_probe.hip:
+#   bash scripts/kres.sh variants/<name>.log probe
 # With `denoise`: the denoiser's kernels (vr_denoise.hip):
 #   bash scripts/kres.sh variants/<name>.log denoise
 # With `atlas`: the atlas and surface-at kernels (vr_atlas.hip):
@@ -42,6 +46,26 @@ if len(sys.argv) > 2 and sys.argv[2] == "atlas":
         if m:
             lab = m.group(1) + ({"0": "<at>", "1": "<atlas>"}.get(m.group(3), ""))
             print(f"{lab:28s} " + " ".join(f"{r.get(c, 0):{w}d}" for c, w in zip(cols, (5, 6, 6, 7, 6, 5))))
+    sys.exit(0)
+if len(sys.argv) > 2 and sys.argv[2] == "probe":
+    CLS, ALL = 1 << 30, 511
+    sets = [("class Cornell+mesh", CLS + 253, (16, 24, 32, 64)), ("class HDRI+mesh", CLS + 252, (16, 24, 32, 64)),
+            ("generic (strict)", ALL, (16, 24, 32, 64)), ("class Cornell spheres", CLS + 247, (16,)),
+            ("class HDRI spheres", CLS + 246, (16,))]
+    cols = ("VGPRs", "VGPRs Spill", "SGPRs Spill", "ScratchSize [bytes/lane]", "LDS Size [bytes/block]", "Occupancy [waves/SIMD]")
+    print(f"{'kernel':44s} {'VGPRs':>5s} {'vspill':>6s} {'sspill':>6s} {'scratch':>7s} {'LDS':>6s} {'waves':>5s}")
+    def row(lab, name):
+        r = recs.get(name)
+        if r is None:
+            print(f"{lab:44s} (not in this build)")
+        else:
+            print(f"{lab:44s} " + " ".join(f"{r.get(c, 0):{w}d}" for c, w in zip(cols, (5, 6, 6, 7, 6, 5))))
+    for lab, feat, stacks in sets:
+        for st in stacks:
+            row(f"ray_radiance_kernel<{st}> {lab}", f"_ZN2vr19ray_radiance_kernelILi{st}ELj{feat}EEEvNS_12RenderParamsENS_11RayRadianceE")
+            row(f"  probe_sh_kernel<{st}> {lab}", f"_ZN2vr15probe_sh_kernelILi{st}ELj{feat}EEEvNS_12RenderParamsENS_7ProbeSHE")
+    row("probe_sum_kernel", "_ZN2vr16probe_sum_kernelEPKfjmPf")
+    row("sh_irradiance_kernel", "_ZN2vr20sh_irradiance_kernelENS_12SHIrradianceE")
     sys.exit(0)
 QUERIES = {"radiance": ("ray_radiance_kernel", "RayRadiance"), "surface": ("ray_surface_kernel", "RaySurface"),
            "shade": ("surface_shade_kernel", "SurfaceShade")}

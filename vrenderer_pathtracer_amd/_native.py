@@ -64,6 +64,8 @@ _SIGNATURES = {
     "vrhip_flat_sah_cost": (ctypes.c_int, [_f, ctypes.c_size_t, _f, ctypes.c_size_t, ctypes.POINTER(ctypes.c_double)]),
     "vrhip_trace_rays": (ctypes.c_int, [_ctx, _vp, _vp, _vp, ctypes.c_uint32, ctypes.c_uint32, _vp]),
     "vrhip_trace_radiance": (ctypes.c_int, [_ctx, _vp, _vp, _vp, ctypes.c_uint32, ctypes.c_uint32, _vp]),
+    "vrhip_probe_sh": (ctypes.c_int, [_ctx, _vp, _vp, _vp, _vp, _vp, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, _vp]),
+    "vrhip_sh_irradiance": (ctypes.c_int, [_ctx, _vp, ctypes.c_uint32, _vp, _vp, ctypes.c_uint32, _vp]),
     "vrhip_trace_surface": (ctypes.c_int, [_ctx, _vp, _vp, ctypes.c_uint32, _vp]),
     "vrhip_shade_surface": (ctypes.c_int, [_ctx, _vp, _vp, _vp, ctypes.c_uint32, ctypes.c_uint32, _vp]),
     "vrhip_camera_rays": (ctypes.c_int, [_ctx, _vp, _vp]),

@@ -22,11 +22,13 @@ SOURCES = ["vr_spec_generic.hip", "vr_cls_cornell_mesh.hip", "vr_cls_hdri_mesh.h
            "vr_radiance_cornell_mesh.hip", "vr_radiance_hdri_mesh.hip", "vr_radiance.hip", "vr_radiance_sphere.hip",
            "vr_surface_cornell_mesh.hip", "vr_surface_hdri_mesh.hip", "vr_surface.hip", "vr_surface_sphere.hip",
            "vr_shade_cornell_mesh.hip", "vr_shade_hdri_mesh.hip", "vr_shade.hip", "vr_shade_sphere.hip", "vr_denoise.hip", "vr_atlas.hip",
+           "vr_probe_cornell_mesh.hip", "vr_probe_hdri_mesh.hip", "vr_probe.hip", "vr_probe_sphere.hip",
            "vr_selftest_hoisted.hip",
            "vrhip_scene.cpp", "vrhip_mesh.cpp", "vrhip_query.cpp", "vrhip_service.cpp", "vrhip_render.cpp", "vrhip_multi.cpp",
            "vrhip_selftest.cpp", "vr_mesh_layout.cpp", "vr_raycast.cpp", "vr_bvh.cpp", "vr_exr.cpp", "vr_merl.cpp"]
 HEADERS = ["vr_params.hpp", "vr_math.hpp", "vr_bvh.hpp", "vr_exr.hpp", "vr_merl.hpp", "vr_kernel.hpp", "vr_devmesh.hpp", "vr_devmesh_dev.hpp", "vr_devbvh.hpp", "vr_devsah.hpp", "vr_refit.hpp", "vr_rayquery.hpp",
            "vr_radiance.hpp", "vr_radiance_dev.hpp", "vr_surface.hpp", "vr_surface_dev.hpp", "vr_shade.hpp", "vr_shade_dev.hpp", "vr_denoise.hpp", "vr_atlas.hpp",
+           "vr_probe.hpp", "vr_probe_dev.hpp",
            "vr_ctx.hpp", "vr_mesh_layout.hpp"]
 ARCH = os.environ.get("VRHIP_OFFLOAD_ARCH", "gfx950")
 

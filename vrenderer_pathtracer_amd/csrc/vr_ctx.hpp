@@ -225,6 +225,9 @@ struct vrhip_ctx {
     // vrhip_atlas_surface scratch, grown on demand and kept: the cell planes
     // and the queue of large triangles (vr_atlas.hpp atlas_scratch_bytes)
     uint8_t* atlas_scratch = nullptr; size_t atlas_bytes = 0;
+    // vrhip_probe_sh scratch, grown on demand and kept: the block partials of
+    // a call with more than 64 directions (vr_probe.hpp probe_scratch_bytes)
+    float* probe_scratch = nullptr; size_t probe_bytes = 0;
     // GL interop (colour, depth textures registered by the display host)
     hipGraphicsResource_t gl_res[2] = { nullptr, nullptr };
     // render service (vrhip_set_service): a session of launches on one

@@ -7,6 +7,54 @@
 
 namespace vr {
 
+// The per-ray sequence of the radiance query for a valid ray, shared by every
+// kernel that enters the path tracer from a caller's ray (ray_radiance_kernel
+// below, probe_sh_kernel in vr_probe_dev.hpp): intersect_scene once, the
+// shared escape of HDRI scenes, then trace<> per path and the mean in path
+// order.  cam is the normalised ray; s1, s2 are left where the last path ends.
+template <int STACK, uint32_t FEAT>
+__device__ __forceinline__ vr4 radiance_along(const RenderParams& p, const Ray& cam, uint32_t& s1, uint32_t& s2,
+                                              const uint32_t n_samples, const float coef, const Lds& L)
+{
+    Cnt cnt;
+    HitRec hr0;
+    const bool hit0 = intersect_scene<STACK, false, FEAT>(p, cam, hr0, L, cnt);
+    // render_kernel's shared escape: in an HDRI scene a ray that
+    // escapes gives every path the first bounce's miss branch, which
+    // draws no random number
+    const bool shared_miss = !HAS(F_CORNELL) && !hit0;
+    vr4 miss_r = mk4(0.f, 0.f, 0.f, 0.f);
+    if (shared_miss) {
+        PathState ps;
+        uint32_t d0 = 0, d1 = 0;
+        path_begin(ps, d0, d1);
+        Ray r0 = cam;
+        (void)bounce_step<false, FEAT>(p, r0, hr0, ps, miss_r, cnt);
+    }
+    vr4 io = mk4(0.f, 0.f, 0.f, 0.f);
+    float last_w = 0.f;
+#pragma unroll 1
+    for (uint32_t k = 0; k < n_samples; ++k) {
+        float depth = 1.f;
+        vr4 result = miss_r;
+        // a path leaves its seeds one hash on, where the next one starts (:620-622)
+        if (!shared_miss) result = trace<STACK, false, FEAT>(p, cam, hr0, hit0, s1, s2, L, cnt, depth);
+        io = add4(io, mul4s(result, coef));
+        last_w = result.w;
+    }
+    return mk4(io.x, io.y, io.z, last_w);
+}
+
+// The query's validity rule: false for inf and NaN; a zero direction and one
+// whose squared length overflows have no unit vector.
+__device__ __forceinline__ bool radiance_ray_valid(const vr4 o, const vr4 dv)
+{
+    const float big = 3.402823466e38f;
+    const float dd = dot4(dv, dv);
+    return fabsf(o.x) <= big && fabsf(o.y) <= big && fabsf(o.z) <= big &&
+           fabsf(dv.x) <= big && fabsf(dv.y) <= big && fabsf(dv.z) <= big && dd > 0.f && dd <= big;
+}
+
 // One ray per lane, in ray_query_kernel's shape: a block fills its node cache
 // once, then each of its waves takes 64-ray chunks in a grid-stride loop over
 // at most one resident set of blocks.  Lanes past the last ray and lanes
@@ -29,7 +77,6 @@ ray_radiance_kernel(const RenderParams p, const RayRadiance q)
     const uint64_t n_chunks = ((uint64_t)q.n_rays + 63u) / 64u;
     const uint64_t n_waves = (uint64_t)gridDim.x * kWaves;
     const uint64_t lane = (uint64_t)(tid & 63);
-    const float big = 3.402823466e38f;
     const float coef = 1.f / (float)q.n_samples;
     for (uint64_t chunk = (uint64_t)blockIdx.x * kWaves + (uint64_t)(tid >> 6); chunk < n_chunks; chunk += n_waves) {
         const uint64_t i = chunk * 64u + lane;
@@ -40,40 +87,11 @@ ray_radiance_kernel(const RenderParams p, const RayRadiance q)
         cam.o = mk4(o[0], o[1], o[2], 0.f);
         const vr4 dv = mk4(d[0], d[1], d[2], 0.f);
         uint32_t s1 = q.seeds[2u * i], s2 = q.seeds[2u * i + 1u];
-        const float dd = dot4(dv, dv);
-        // false for inf and NaN; a zero direction and one whose squared length overflows have no unit vector
-        const bool valid = fabsf(cam.o.x) <= big && fabsf(cam.o.y) <= big && fabsf(cam.o.z) <= big &&
-                           fabsf(dv.x) <= big && fabsf(dv.y) <= big && fabsf(dv.z) <= big && dd > 0.f && dd <= big;
+        const bool valid = radiance_ray_valid(cam.o, dv);
         vr4 rec = mk4(0.f, 0.f, 0.f, 0.f);
         if (valid) {
             cam.d = normalize4(dv);                      // the reference's camera ray (:842-844)
-            Cnt cnt;
-            HitRec hr0;
-            const bool hit0 = intersect_scene<STACK, false, FEAT>(p, cam, hr0, L, cnt);
-            // render_kernel's shared escape: in an HDRI scene a ray that
-            // escapes gives every path the first bounce's miss branch, which
-            // draws no random number
-            const bool shared_miss = !HAS(F_CORNELL) && !hit0;
-            vr4 miss_r = mk4(0.f, 0.f, 0.f, 0.f);
-            if (shared_miss) {
-                PathState ps;
-                uint32_t d0 = 0, d1 = 0;
-                path_begin(ps, d0, d1);
-                Ray r0 = cam;
-                (void)bounce_step<false, FEAT>(p, r0, hr0, ps, miss_r, cnt);
-            }
-            vr4 io = mk4(0.f, 0.f, 0.f, 0.f);
-            float last_w = 0.f;
-#pragma unroll 1
-            for (uint32_t k = 0; k < q.n_samples; ++k) {
-                float depth = 1.f;
-                vr4 result = miss_r;
-                // a path leaves its seeds one hash on, where the next one starts (:620-622)
-                if (!shared_miss) result = trace<STACK, false, FEAT>(p, cam, hr0, hit0, s1, s2, L, cnt, depth);
-                io = add4(io, mul4s(result, coef));
-                last_w = result.w;
-            }
-            rec = mk4(io.x, io.y, io.z, last_w);
+            rec = radiance_along<STACK, FEAT>(p, cam, s1, s2, q.n_samples, coef, L);
         }
         q.radiance[i] = rec;                             // one 16-B store per ray
     }

@@ -8,7 +8,10 @@
 // query's records into an image (vrhip_denoise, vrhip_denoise_frame, vr_denoise.hip),
 // and the records that need no ray: at points of the resident mesh
 // (vrhip_surface_at) and at the texels of a lightmap atlas of its uvs
-// (vrhip_atlas_surface, vr_atlas.hip).  All read the scene
+// (vrhip_atlas_surface, vr_atlas.hip), and the probe query: radiance from
+// points along one shared direction set, projected onto spherical harmonics
+// in the call (vrhip_probe_sh, vr_probe.hip), with the irradiance those
+// coefficients give at a normal (vrhip_sh_irradiance).  All read the scene
 // only: the accumulation, the images and the frame counter stay as they are.
 #include <cstddef>
 #include <cmath>
@@ -17,6 +20,7 @@
 #include "vr_atlas.hpp"
 #include "vr_ctx.hpp"
 #include "vr_denoise.hpp"
+#include "vr_probe.hpp"
 #include "vr_radiance.hpp"
 #include "vr_rayquery.hpp"
 #include "vr_shade.hpp"
@@ -78,6 +82,83 @@ int vrhip_trace_radiance(vrhip_ctx* c, const float* d_origins, const float* d_di
     (void)hipGetLastError();            // the launch below reports its own error only
     const int e = vr::launch_ray_radiance(p, q, mesh_stack_entries(c->mesh.a.depth), c->cu_count, c->stream);
     if (e) return fail(VRHIP_ERR_HIP, std::string("radiance query: ") + hipGetErrorString((hipError_t)e));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return svc_verify(c);
+}
+
+// Grows the probe scratch to `bytes` (the new buffer before the old one goes,
+// as denoise_scratch).
+static int probe_scratch(vrhip_ctx* c, size_t bytes)
+{
+    if (c->probe_bytes >= bytes) return VRHIP_OK;
+    void* raw = nullptr;
+    if (hipMalloc(&raw, bytes) != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(VRHIP_ERR_NOMEM, "probe scratch: " + std::to_string(bytes) + " bytes");
+    }
+    if (c->probe_scratch) {
+        (void)hipStreamSynchronize(c->stream);
+        (void)hipFree((void*)c->probe_scratch);
+    }
+    c->probe_scratch = (float*)raw; c->probe_bytes = bytes;
+    return VRHIP_OK;
+}
+
+// Probe radiance on spherical harmonics: vrhip_trace_radiance's scene, session
+// handling and order of checks, ray (i, k) = (point i, direction k) traced and
+// reduced in one call (include/vrhip.h has the definition).
+static_assert(VRHIP_PROBE_BLOCK == (int)vr::kProbeBlock && VRHIP_PROBE_WORDS == (int)vr::kProbeWords,
+              "the block and the record of vrhip_probe_sh");
+int vrhip_probe_sh(vrhip_ctx* c, const float* d_points, const float* d_dirs, const float* d_weights,
+                   const uint32_t* d_probe_seeds, const uint32_t* d_dir_seeds, uint32_t n_probes, uint32_t n_dirs,
+                   uint32_t n_samples, float* d_sh)
+{
+    if (!c) return fail(VRHIP_ERR_INVALID, "null ctx");
+    if (n_probes > 0 && (!d_points || !d_dirs || !d_probe_seeds || !d_dir_seeds || !d_sh))
+        return fail(VRHIP_ERR_INVALID, "null point, direction, seed or coefficient array");
+    if (((uintptr_t)d_sh & 15u) != 0u) return fail(VRHIP_ERR_INVALID, "d_sh is not 16-byte aligned");
+    if (n_samples < 1u || n_samples > vr::kRadianceMaxSamples)
+        return fail(VRHIP_ERR_INVALID, "n_samples is " + std::to_string(n_samples) + " (1 to " +
+                                           std::to_string(vr::kRadianceMaxSamples) + ")");
+    if (n_dirs < 1u || n_dirs > vr::kProbeMaxDirs)
+        return fail(VRHIP_ERR_INVALID, "n_dirs is " + std::to_string(n_dirs) + " (1 to " +
+                                           std::to_string(vr::kProbeMaxDirs) + ")");
+    if (!c->group.empty()) return refuse_multi(c, "vrhip_probe_sh");
+    if (n_probes == 0) return VRHIP_OK;
+    if (!c->cornell && !c->hdr)
+        return fail(VRHIP_ERR_NO_ENV, "HDRI mode needs an environment map (vrhip_upload_hdr)");
+    int rc = set_device(c); if (rc) return rc;
+    if ((rc = svc_close(c)) != VRHIP_OK) return rc;
+    if ((rc = probe_scratch(c, vr::probe_scratch_bytes(n_probes, n_dirs))) != VRHIP_OK) return rc;
+    vr::RenderParams p;
+    std::memset(&p, 0, sizeof(p));
+    scene_params(c, p);
+    const vr::ProbeSH q{ d_points, d_dirs, d_weights, d_probe_seeds, d_dir_seeds, n_probes, n_dirs, n_samples,
+                         12.566370614f / (float)n_dirs, c->probe_scratch, d_sh };
+    (void)hipGetLastError();            // the launches below report their own errors only
+    const int e = vr::launch_probe_sh(p, q, mesh_stack_entries(c->mesh.a.depth), c->cu_count, c->stream);
+    if (e) return fail(VRHIP_ERR_HIP, std::string("probe query: ") + hipGetErrorString((hipError_t)e));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return svc_verify(c);
+}
+
+// Irradiance at a normal from the records of vrhip_probe_sh: no scene, no mesh.
+int vrhip_sh_irradiance(vrhip_ctx* c, const float* d_sh, uint32_t m, const uint32_t* d_index, const float* d_normals,
+                        uint32_t n, float* d_out)
+{
+    if (!c) return fail(VRHIP_ERR_INVALID, "null ctx");
+    if (n > 0 && (!d_sh || !d_normals || !d_out)) return fail(VRHIP_ERR_INVALID, "null coefficient, normal or output array");
+    if (((uintptr_t)d_out & 15u) != 0u) return fail(VRHIP_ERR_INVALID, "d_out is not 16-byte aligned");
+    if (n > 0 && !d_index && n != m)
+        return fail(VRHIP_ERR_INVALID, "no index: n is " + std::to_string(n) + ", m is " + std::to_string(m));
+    if (!c->group.empty()) return refuse_multi(c, "vrhip_sh_irradiance");
+    if (n == 0) return VRHIP_OK;
+    int rc = set_device(c); if (rc) return rc;
+    if ((rc = svc_close(c)) != VRHIP_OK) return rc;
+    const vr::SHIrradiance q{ d_sh, m, d_index, d_normals, n, (vr4*)d_out };
+    (void)hipGetLastError();            // the launch below reports its own error only
+    const int e = vr::launch_sh_irradiance(q, c->stream);
+    if (e) return fail(VRHIP_ERR_HIP, std::string("sh irradiance: ") + hipGetErrorString((hipError_t)e));
     HIP_TRY(hipStreamSynchronize(c->stream));
     return svc_verify(c);
 }

@@ -160,7 +160,7 @@ int vrhip_destroy(vrhip_ctx* c)
     dfree(c->hdr); dfree(c->tex[0]); dfree(c->tex[1]); dfree(c->tex[2]); dfree(c->brdf);
     for (int i = 0; i < 2; ++i)
         if (c->gl_res[i]) (void)hipGraphicsUnregisterResource(c->gl_res[i]);
-    dfree(c->counters); dfree(c->tone_t); dfree(c->dn_planes); dfree(c->dn_frame); dfree(c->atlas_scratch);
+    dfree(c->counters); dfree(c->tone_t); dfree(c->dn_planes); dfree(c->dn_frame); dfree(c->atlas_scratch); dfree(c->probe_scratch);
     if (c->comm) (void)ncclCommDestroy(c->comm);
     dfree(c->comm_send); dfree(c->comm_recv);
     for (auto& l : c->lane) {

@@ -572,6 +572,78 @@ class VRendererHIP:
                                             ctypes.c_void_p(out.data_ptr())), "vrhip_shade_surface")
         return out
 
+    def probeSH(self, points, dirs, weights=None, probe_seeds=None, dir_seeds=None, samples: int = 2):
+        """What light arrives at these points, as nine spherical-harmonic
+        coefficients per colour channel (vrhip_probe_sh)?  Ray (i, k) is the
+        ray traceRadiance would trace from points[i] along dirs[k] with the
+        seed pair probe_seeds[i] ^ dir_seeds[k]; its radiance is projected on
+        the real SH basis to band 2 and summed over k in a fixed order inside
+        the call, so no (N * K) buffer exists.  points: (N,3) float32 torch
+        tensor on the renderer's GPU, contiguous.  dirs: (K,3) float32, one
+        set shared by all probes (1 to 65536; scenes.probe_directions),
+        normalised by the library.  weights: (K,) float32 quadrature weights,
+        used as given; None weighs every direction 4 pi / K.  probe_seeds:
+        (N,2), dir_seeds: (K,2) uint32 or int32; None draws them with
+        torch.randint on that device.  samples: paths per ray (1 to 4096).
+        Returns an (N,28) float32 device tensor: out[:, :27].view(N, 9, 3) is
+        coefficient j of channel c, out[:, 27].view(torch.int32) the number of
+        valid rays of the probe (a non-finite point or a direction of zero,
+        non-finite or overflowing length contributes +0).  ValueError for a
+        wrong device, dtype, shape or layout.  Synchronises torch's current
+        stream first; the query runs on the renderer's own stream and has
+        finished on return."""
+        import torch
+        self._need_ctx()
+        dev = self._torch_device()
+        int_types = tuple(t for t in (torch.int32, getattr(torch, "uint32", None)) if t is not None)
+        ptr = self._tensor_ptr
+        p_p = ptr("points", points, 3, (torch.float32,))
+        p_d = ptr("dirs", dirs, 3, (torch.float32,))
+        if p_p is None or p_d is None:
+            raise ValueError("points and dirs are required")
+        n, k = int(points.shape[0]), int(dirs.shape[0])
+        p_w = ptr("weights", weights, None, (torch.float32,), k)
+        if probe_seeds is None:
+            probe_seeds = torch.randint(-2**31, 2**31, (n, 2), dtype=torch.int32, device=f"cuda:{dev}")
+        if dir_seeds is None:
+            dir_seeds = torch.randint(-2**31, 2**31, (k, 2), dtype=torch.int32, device=f"cuda:{dev}")
+        p_ps = ptr("probe_seeds", probe_seeds, 2, int_types, n)
+        p_ds = ptr("dir_seeds", dir_seeds, 2, int_types, k)
+        out = torch.empty((n, 28), dtype=torch.float32, device=f"cuda:{dev}")
+        torch.cuda.current_stream(dev).synchronize()
+        check(self._lib.vrhip_probe_sh(self._ctx, p_p, p_d, p_w, p_ps, p_ds, n, k, int(samples),
+                                       ctypes.c_void_p(out.data_ptr())), "vrhip_probe_sh")
+        return out
+
+    def shIrradiance(self, sh, normals, index=None):
+        """The irradiance the records of probeSH give at these normals
+        (vrhip_sh_irradiance): the nine coefficients of each channel against
+        the clamped-cosine lobe (pi, 2 pi / 3, pi / 4).  sh: (M,28) float32 on
+        the renderer's GPU, contiguous.  normals: (N,3) float32, used as given
+        (not normalised).  index: (N,) uint32 or int32, the record of each
+        output; None takes record q for output q (then N == M).  Returns an
+        (N,4) float32 device tensor (E.r, E.g, E.b, 0); an index of M or more
+        gives zeros.  Needs no scene.  ValueError for a wrong device, dtype,
+        shape or layout."""
+        import torch
+        self._need_ctx()
+        dev = self._torch_device()
+        int_types = tuple(t for t in (torch.int32, getattr(torch, "uint32", None)) if t is not None)
+        ptr = self._tensor_ptr
+        p_s = ptr("sh", sh, 28, (torch.float32,))
+        p_n = ptr("normals", normals, 3, (torch.float32,))
+        if p_s is None or p_n is None:
+            raise ValueError("sh and normals are required")
+        m, n = int(sh.shape[0]), int(normals.shape[0])
+        p_i = ptr("index", index, None, int_types, n)
+        if index is None and n != m:
+            raise ValueError(f"normals: shape {tuple(normals.shape)} (expected ({m}, 3) without an index)")
+        out = torch.empty((n, 4), dtype=torch.float32, device=f"cuda:{dev}")
+        torch.cuda.current_stream(dev).synchronize()
+        check(self._lib.vrhip_sh_irradiance(self._ctx, p_s, m, p_i, p_n, n, ctypes.c_void_p(out.data_ptr())),
+              "vrhip_sh_irradiance")
+        return out
+
     def diffuseRecords(self, points, normals, color=None):
         """The (N,28) records of a white (or `color`ed) diffuse surface at
         these points and normals, for shadeSurface: what a lightmap texel or

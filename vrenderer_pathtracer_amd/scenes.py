@@ -109,6 +109,39 @@ def torus_knot_unwrapped(nu: int = 100, nv: int = 50, margin: float = 0.0, p: in
                 uvs=np.stack([uu, vv], -1).reshape(-1, 2).astype(np.float32), tris=tris.astype(np.uint32))
 
 
+def probe_directions(k: int, compact: bool = True):
+    """A direction set for VRendererHIP.probeSH: (dirs [k,3] float32, weights
+    [k] float32).  The Fibonacci sphere z_i = 1 - (2i + 1) / k, phi_i = i * pi *
+    (3 - sqrt 5), computed in float64 and cast; the weights are equal, the
+    float32 quotient 12.566370614 / k that probeSH uses without weights.
+    compact: the directions are sorted by the Morton code of their octahedral
+    map (16 bits a side), so that each block of 64 consecutive directions,
+    which share a GPU wave, is a compact cap of the sphere.  The order is a
+    cost lever only: the set and its weights are the same."""
+    k = int(k)
+    if k < 1:
+        raise ValueError("k must be at least 1")
+    i = np.arange(k, dtype=np.float64)
+    z = 1.0 - (2.0 * i + 1.0) / k
+    r = np.sqrt(np.maximum(0.0, 1.0 - z * z))
+    phi = i * (math.pi * (3.0 - math.sqrt(5.0)))
+    d = np.stack([r * np.cos(phi), r * np.sin(phi), z], -1)
+    if compact:
+        o = d / np.abs(d).sum(-1, keepdims=True)
+        u, v = o[:, 0].copy(), o[:, 1].copy()
+        low = o[:, 2] < 0.0                              # fold the lower half over the diagonals
+        u[low] = (1.0 - np.abs(o[low, 1])) * np.where(o[low, 0] >= 0.0, 1.0, -1.0)
+        v[low] = (1.0 - np.abs(o[low, 0])) * np.where(o[low, 1] >= 0.0, 1.0, -1.0)
+        q = [np.minimum((c * 0.5 + 0.5) * 65536.0, 65535.0).astype(np.uint64) for c in (u, v)]
+        key = np.zeros(k, np.uint64)
+        for bit in range(16):
+            key |= ((q[0] >> np.uint64(bit)) & np.uint64(1)) << np.uint64(2 * bit)
+            key |= ((q[1] >> np.uint64(bit)) & np.uint64(1)) << np.uint64(2 * bit + 1)
+        d = d[np.argsort(key, kind="stable")]
+    w = np.full(k, np.float32(12.566370614) / np.float32(k), np.float32)
+    return np.ascontiguousarray(d.astype(np.float32)), w
+
+
 def procedural_hdr(w: int = 2048, h: int = 1024, seed: int = 7) -> np.ndarray:
     """Equirect environment (rows = acos(dir.y)/pi, cols = atan2(x,z)/2pi as
     sampled at PathTracer.cu:636-643): sky gradient, ground, a sun disc and
