@@ -79,6 +79,42 @@ int vrhip_destroy(vrhip_ctx *ctx);
 /* Run subsequent work on this hipStream_t (NULL = the context's own stream). */
 int vrhip_set_stream(vrhip_ctx *ctx, void *hip_stream);
 void *vrhip_get_stream(vrhip_ctx *ctx);
+/* Streams.  A context has one "context stream": its own (created
+ * non-blocking with the context, so it does not synchronise with the NULL
+ * stream) or the one vrhip_set_stream gave it; vrhip_get_stream returns it.
+ * vrhip_set_stream waits for the stream it leaves, so work does not reorder
+ * across the change; it is refused on a multi-device context.
+ *   Where the work runs.  Uploads, clears, the device mesh builds and the
+ * refit, every query (vrhip_trace_rays/radiance/surface, vrhip_shade_surface,
+ * vrhip_probe_sh, vrhip_sh_irradiance, vrhip_surface_at, vrhip_atlas_surface,
+ * vrhip_camera_rays, vrhip_denoise, vrhip_denoise_frame), the read-backs,
+ * vrhip_pack_tiles/unpack_tiles and vrhip_comm_gather are queued on the
+ * context stream in call order.  vrhip_render's path kernels run there too
+ * or on internal streams (the path streams, the render service's), ordered
+ * by events against the context stream; what writes the accumulation and the
+ * images -- the finish pass, or a sphere scene's render kernel -- always runs
+ * on the context stream.
+ *   Device inputs (the d_ arguments of the device uploads, the refit and the
+ * queries) must be complete, or pending on the context stream: work queued
+ * there before the call -- the kernel that still produces the rays, a copy --
+ * is ordered ahead of the library's reads.  Work on any OTHER stream, the NULL
+ * stream included, is not waited for: synchronise it or make the context
+ * stream wait for its event first.
+ *   After vrhip_render, a caller that holds the context stream or the buffers
+ * (vrhip_set_stream, vrhip_get_stream, vrhip_device_buffers, taken BEFORE the
+ * render) may queue its own work on the context stream -- a copy out of the
+ * buffers, a collective -- with no library call in between, and that work
+ * sees every frame of the renders before it:
+ *   service mode -1 (automatic, the default) and 0: always.  Such a context
+ *     never joins a render service session on its own, because a session's
+ *     images arrive with the finish pass that its close enqueues.
+ *   service mode 1 (explicit): after the next call that closes the session
+ *     (the list is at vrhip_set_service; vrhip_device_buffers is one).  The
+ *     close waits for nothing on the host: it enqueues the finish pass on the
+ *     context stream, so work queued there behind the closing call sees the
+ *     session's frames.
+ * vrhip_sync on such a context waits for the whole context stream, the
+ * caller's own work on it included. */
 
 /* ---- per-frame state -------------------------------------------------- */
 /* replaces vRendererCuda::updateCamera (src/vRendererCuda.cpp:69-98): copies
@@ -132,7 +168,8 @@ int vrhip_upload_mesh_indexed(vrhip_ctx *ctx, const float *positions, const floa
  * centres (ties by index), L = max(2, ceil(n_tris / max_leaf_tris)) leaves of
  * equal size (+-1), inner nodes halving the leaf range, depth ceil(log2 L); a
  * single triangle is stored twice under two leaves, as the host builder does.
- * The caller's data must be complete before the call; the build runs on the
+ * The caller's data must be complete before the call or pending on the
+ * context stream (see Streams at vrhip_set_stream); the build runs on the
  * context stream and the call returns when it has finished.  Transactional:
  * on any error the resident mesh stays as it was.  VRHIP_ERR_INVALID for null
  * or empty arrays, n_tris >= 2^24, max_leaf_tris > 127 (all before any device

@@ -81,6 +81,25 @@ def test_null_context_is_invalid(native):
                                    None) == -1
 
 
+def test_stream_calls_refuse_a_null_context(native):
+    """vrhip_set_stream and vrhip_get_stream check the context before any
+    device call: -1 whatever the stream, and no stream to hand out."""
+    for handle in (None, 0x1000):
+        assert native.vrhip_set_stream(None, ctypes.c_void_p(handle)) == -1
+        assert b"ctx" in native.vrhip_last_error().lower()
+    assert native.vrhip_get_stream(None) is None
+
+
+def test_device_buffers_refuses_a_null_context(native):
+    """vrhip_device_buffers(NULL, ...) is VRHIP_ERR_INVALID and writes none of
+    its outputs, with or without them."""
+    a, r, d = (ctypes.c_void_p(0x55) for _ in range(3))
+    assert native.vrhip_device_buffers(None, ctypes.byref(a), ctypes.byref(r), ctypes.byref(d)) == -1
+    assert (a.value, r.value, d.value) == (0x55, 0x55, 0x55)
+    assert native.vrhip_device_buffers(None, None, None, None) == -1
+    assert b"ctx" in native.vrhip_last_error().lower()
+
+
 def _mesh_arrays(m):
     return m["positions"], m["tris"]
 

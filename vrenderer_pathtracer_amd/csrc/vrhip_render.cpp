@@ -305,10 +305,17 @@ static int serve(vrhip_ctx* c, RenderCall& q, uint32_t* done)
     // so they keep the launch path)
     const bool c2_exact = p.flags == (vr::F_CORNELL | vr::F_MESH);
     const bool svc_size = ovl_size_mesh || !c->cornell || c2_exact;
+    // a session's images arrive with the finish pass its CLOSE enqueues, at a
+    // later library call: a caller that holds the stream or the buffers
+    // (stream_shared) queues its own reads right behind vrhip_render and must
+    // find the results there, so its context joins a session only when it
+    // asked for one (mode 1) -- the rule the completion flag follows
+    // (launch_decisions)
+    const bool svc_auto = c->service < 0 && !c->stream_shared && svc_size && in_flight && c->overlap != 0;
     // launches whose slots the scratch budget cannot hold twice take the
     // launch path in every mode (4K frames of many frames per launch)
     const bool svc = q.count == 0 && q.wave_kernel && q.stack <= 32 && q.n_tiles > 0 &&
-                     (c->service > 0 || (c->service < 0 && svc_size && in_flight && c->overlap != 0)) &&
+                     (c->service > 0 || svc_auto) &&
                      svc_slots(c, p.path_stride, q.k_max, nullptr) >= 2u;
     if (!svc) return svc_close(c);
     p.n_queues = c->cornell ? VR_QUEUES : VR_QUEUES_HDRI;
